@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: Ray Train tokens/sec, Llama-3-8B DDP (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line: nothing else is
+measured, so ``--full`` (the switch for every secondary measurement) has nothing to add here.
+``--dump-outputs DIR`` saves what the last timed step computed (train/llm.py
+``training_step_outputs``: the loss and a seeded sample of the updated weights and AdamW moments)
+as ``DIR/<name>.npy`` in float32; weights and tokens are seeded, so two builds run with the same
+arguments see identical inputs and can be compared output for output.
 
 Two launch modes, same worker function:
   * self-launched (no torchrun): ``TorchTrainer(num_workers=N, use_gpu=True)`` starts N GPU
@@ -53,6 +60,11 @@ def main():
                     help="run the AdamW update per bucket on a side stream, overlapped with the next forward")
     ap.add_argument("--fused-ce", type=int, default=None, choices=[0, 1],
                     help="1: chunked lm_head + one-pass HIP cross-entropy (no T x V logits); default: model preset")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, save the last step's outputs (loss, a seeded sample of the updated "
+                         "weights and AdamW moments) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; this benchmark has none, so the run is the plain one")
     ap.add_argument("--device", default="cuda", help="cuda (the benchmark) | cpu (gloo rehearsal of the launch path)")
     args = ap.parse_args()
 
@@ -71,6 +83,9 @@ def main():
                    "steps": args.steps, "warmup": args.warmup, "bucket_cap_mb": args.bucket_mb, "parallel": args.parallel,
                    "grad_reduce_dtype": args.grad_reduce_dtype, "device": args.device,
                    "overlap_optimizer": args.overlap_optimizer}
+    if args.dump_outputs:
+        loop_config["dump_outputs"] = os.path.abspath(args.dump_outputs)  # the workers' cwd is not the driver's
+        os.makedirs(loop_config["dump_outputs"], exist_ok=True)
     if args.fused_ce is not None:
         loop_config["model_overrides"] = {"fused_ce": bool(args.fused_ce)}
     # workers' own output stays in their log files: stdout carries exactly one JSON line

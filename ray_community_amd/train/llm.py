@@ -86,9 +86,35 @@ def build_llama_training(model="llama3-8b", seq_len=4096, micro_batch=2, lr=3e-4
     return net, ddp, opt, batch, step
 
 
+def training_step_outputs(ddp, opt, loss, sample: int = 1 << 20, seed: int = 0) -> dict:
+    """What the last training step left behind, as float32 numpy arrays: its loss, and a fixed,
+    seeded sample (``sample`` elements, the same indices for the same model) of the updated
+    weights and of AdamW's two moments -- this rank's shard of them under zero / fsdp. The
+    moments are fp32 running means of the gradients, so they show a changed kernel long before
+    the bf16 weights do."""
+    wait = getattr(opt, "wait_pending_update", None)
+    if wait is not None:
+        wait()
+    flat = getattr(ddp, "flat", None)
+    full = {"weights_sample": flat.data if flat is not None else opt.master,
+            "adam_exp_avg_sample": opt.m, "adam_exp_avg_sq_sample": opt.v}
+    out = {"loss": loss.detach().float().cpu().numpy()}
+    for name, t in full.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > sample:
+            g = torch.Generator()
+            g.manual_seed(seed)
+            idx = torch.randint(0, t.numel(), (sample,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    return out
+
+
 def llama_train_loop_per_worker(config: dict):
     """Train-loop entry point. Config keys: model, seq_len, micro_batch, steps, warmup, lr,
-    bucket_cap_mb. Reports ``tokens_per_s`` (this worker) and ``ms_per_step``."""
+    bucket_cap_mb, dump_outputs (a directory: after the timed steps every rank saves
+    ``training_step_outputs`` of its last step there as ``<name>.npy``, ranks above 0 as
+    ``<name>_rank<r>.npy``). Reports ``tokens_per_s`` (this worker) and ``ms_per_step``."""
     from . import report
 
     dev_kind = config.get("device", "cuda")
@@ -161,5 +187,12 @@ def llama_train_loop_per_worker(config: dict):
         from .torch.config import group_info
 
         metrics["process_group"] = group_info(torch.cuda.current_device())
+    dump_dir = config.get("dump_outputs")
+    if dump_dir and loss is not None:
+        import numpy as np
+
+        os.makedirs(dump_dir, exist_ok=True)
+        for name, arr in training_step_outputs(ddp, opt, loss).items():
+            np.save(os.path.join(dump_dir, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"), arr)
     report(metrics)
     return metrics

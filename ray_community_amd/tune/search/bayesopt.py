@@ -12,7 +12,8 @@ normalised) fitted on every finished trial: ``ucb`` (mean + kappa * std, the def
 The acquisition is maximised by scoring random candidates and refining the best few with
 L-BFGS-B. Suggestions already evaluated (to ``repeat_float_precision`` digits) are skipped; once
 one configuration has been suggested more than ``patience`` times the search ends
-(``Searcher.FINISHED``), as in the reference.
+(``Searcher.FINISHED``), as in the reference. A GP suggestion equal to a trial that is still
+running is not such a repeat: the searcher waits for that trial's result instead.
 """
 from __future__ import annotations
 
@@ -201,6 +202,11 @@ class BayesOptSearch(Searcher):
             flat = self._from_unit(self._rng.uniform(size=len(self._names)))
         else:
             flat = self._from_unit(self._maximize())
+            # the model has learnt nothing since it proposed a point that is still running, so it
+            # proposes it again: wait for that trial. Only repeats of evaluated points count
+            # towards `patience`; otherwise a slow trial ends the search after a few polls.
+            if self._skip_duplicate and any(self._key(f) == self._key(flat) for f in self._live.values()):
+                return None
         key = self._key(flat)
         seen = key in self._counter
         self._counter[key] += 1

@@ -54,6 +54,38 @@ def test_bench_self_launch_two_workers_cpu(tmp_path):
     assert rec["config"]["global_batch"] == 4
 
 
+def test_bench_dump_outputs_is_repeatable_cpu(tmp_path):
+    """``--dump-outputs DIR`` (with ``--full``, which adds nothing to this benchmark): the last timed
+    step's loss and seeded samples of weights and AdamW moments land in DIR as float32 .npy, and a
+    second run with the same arguments starts from the same inputs, so it writes the same arrays."""
+    import numpy as np
+
+    env = dict(os.environ)
+    env.pop("RCA_ADDRESS", None)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
+        env.pop(k, None)
+    runs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--model", "llama3-tiny", "--seq-len", "128", "--device", "cpu", "--full", "--dump-outputs", d]
+        out = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["metric"] == "ray_train_tokens_per_sec_llama3_8b_ddp"
+        arrs = {f[:-4]: np.load(os.path.join(str(tmp_path), d, f)) for f in sorted(os.listdir(tmp_path / d))}
+        assert set(arrs) == {"loss", "weights_sample", "adam_exp_avg_sample", "adam_exp_avg_sq_sample"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert abs(float(arrs["loss"]) - rec["extra"]["loss"]) < 1e-3
+        # three optimizer steps were taken: the moments are populated, not the zeros they start as
+        assert np.abs(arrs["adam_exp_avg_sample"]).max() > 0 and arrs["adam_exp_avg_sq_sample"].min() >= 0
+        runs.append(arrs)
+    for name, a in runs[0].items():
+        np.testing.assert_allclose(runs[1][name], a, rtol=1e-5, atol=1e-7, err_msg=name)
+
+
 def test_bench_data_serve_pipeline_cpu(tmp_path):
     """Config 5 plumbing: Data read -> map_batches actor pool -> Serve handle -> replica, on CPU."""
     env = dict(os.environ)

@@ -62,6 +62,22 @@ def test_waits_for_random_phase_log_space_duplicates_and_state(tmp_path):
     assert isinstance(create_searcher("bayesopt", space={"x": (0, 1)}, metric="m", mode="min"), BayesOptSearch)
 
 
+def test_polling_while_a_suggested_trial_runs_does_not_end_the_search():
+    """With the same finished trials the GP proposes the same point again; a controller that polls
+    for work while that trial is still running must be told to wait, however often it asks."""
+    f = lambda c: -(c["a"] - 2.0) ** 2  # noqa: E731
+    s = BayesOptSearch({"a": tune.uniform(0.0, 5.0)}, metric="score", mode="max", random_search_steps=4,
+                       random_state=1)
+    for i in range(4):
+        s.on_trial_complete(f"r{i}", {"score": f(s.suggest(f"r{i}"))})
+    running = s.suggest("g0")
+    assert running is not None and running != Searcher.FINISHED
+    assert [s.suggest(f"poll{i}") for i in range(8)] == [None] * 8  # more polls than `patience`
+    s.on_trial_complete("g0", {"score": f(running)})
+    nxt = s.suggest("g1")
+    assert nxt not in (None, Searcher.FINISHED) and nxt != running
+
+
 def test_with_tuner(shutdown_only, tmp_path):
     ray.init(num_cpus=2)
 
