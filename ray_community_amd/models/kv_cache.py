@@ -1,0 +1,102 @@
+"""Paged KV cache for Llama generation.
+
+Per layer the cache is two tensors ``[num_blocks, page_size, Hk, D]``; a sequence owns a list of
+blocks (in logical order) and token ``i`` of it lives in slot ``blocks[i // page_size] * page_size
++ i % page_size``. Every block id and slot handed to the kernels (``ops.kv_cache_append_``,
+``ops.paged_attention_decode``) comes from this allocator, which is what keeps them in range.
+"""
+from __future__ import annotations
+
+from typing import Dict, Hashable, List, Optional, Sequence
+
+import torch
+
+
+class KVCacheFull(RuntimeError):
+    """The paged KV cache has too few free blocks for the request (nothing was allocated)."""
+
+
+class PagedKVCache:
+    def __init__(self, cfg, num_blocks: int, page_size: int = 16, device=None, dtype=torch.bfloat16):
+        if num_blocks <= 0 or page_size <= 0:
+            raise ValueError("num_blocks and page_size must be positive")
+        self.cfg = cfg
+        self.num_blocks = int(num_blocks)
+        self.page_size = int(page_size)
+        self.device = torch.device(device if device is not None else "cpu")
+        self.dtype = dtype
+        shape = (self.num_blocks, self.page_size, cfg.num_kv_heads, cfg.head_dim)
+        # uninitialised on purpose: slots past a sequence's length are never read
+        self.k = [torch.empty(shape, device=self.device, dtype=dtype) for _ in range(cfg.num_layers)]
+        self.v = [torch.empty(shape, device=self.device, dtype=dtype) for _ in range(cfg.num_layers)]
+        self._free: List[int] = list(range(self.num_blocks - 1, -1, -1))  # stack: block 0 goes first
+        self._blocks: Dict[Hashable, List[int]] = {}
+        self._lens: Dict[Hashable, int] = {}
+
+    @property
+    def num_free_blocks(self) -> int:
+        return len(self._free)
+
+    def blocks_needed(self, seq_id, n_tokens: int) -> int:
+        """Blocks ``allocate(seq_id, n_tokens)`` would take from the free list."""
+        have = len(self._blocks.get(seq_id, ()))
+        total = self._lens.get(seq_id, 0) + int(n_tokens)
+        return max(0, -(-total // self.page_size) - have)
+
+    def allocate(self, seq_id, n_tokens: int) -> List[int]:
+        """Grow ``seq_id`` (created on first use) by ``n_tokens``; returns the new tokens' slots."""
+        if n_tokens < 0:
+            raise ValueError("n_tokens must be >= 0")
+        need = self.blocks_needed(seq_id, n_tokens)
+        if need > len(self._free):
+            raise KVCacheFull(f"need {need} blocks for {n_tokens} more tokens of sequence {seq_id!r}, "
+                              f"{len(self._free)} of {self.num_blocks} free")
+        blocks = self._blocks.setdefault(seq_id, [])
+        for _ in range(need):
+            blocks.append(self._free.pop())
+        start = self._lens.get(seq_id, 0)
+        self._lens[seq_id] = start + int(n_tokens)
+        P = self.page_size
+        return [blocks[i // P] * P + i % P for i in range(start, start + int(n_tokens))]
+
+    def free(self, seq_id) -> None:
+        """Return the blocks of ``seq_id`` to the free list (unknown ids are ignored)."""
+        self._free.extend(reversed(self._blocks.pop(seq_id, [])))
+        self._lens.pop(seq_id, None)
+
+    def rollback(self, seq_id, n_tokens: int) -> None:
+        """Undo the last ``n_tokens`` of ``seq_id``: blocks they alone occupied go back to the free
+        list (in the order ``allocate`` would hand them out again), and a sequence left with no
+        tokens is forgotten."""
+        have = self._lens.get(seq_id, 0)
+        if n_tokens < 0 or n_tokens > have:
+            raise ValueError(f"cannot roll back {n_tokens} of {have} tokens of sequence {seq_id!r}")
+        left = have - int(n_tokens)
+        blocks = self._blocks.get(seq_id, [])
+        keep = -(-left // self.page_size)
+        while len(blocks) > keep:
+            self._free.append(blocks.pop())
+        if left == 0:
+            self._blocks.pop(seq_id, None)
+            self._lens.pop(seq_id, None)
+        else:
+            self._lens[seq_id] = left
+
+    def length(self, seq_id) -> int:
+        return self._lens.get(seq_id, 0)
+
+    def blocks_held(self, seq_id) -> int:
+        return len(self._blocks.get(seq_id, ()))
+
+    def block_table(self, seq_ids: Sequence[Optional[Hashable]]) -> torch.Tensor:
+        """int32 ``[len(seq_ids), max_blocks]`` on the cache's device, rows padded with 0 (the
+        kernels never read past a sequence's length). ``None`` / unknown ids give an empty row."""
+        rows = [self._blocks.get(s, []) if s is not None else [] for s in seq_ids]
+        width = max([len(r) for r in rows] + [1])
+        table = [r + [0] * (width - len(r)) for r in rows]
+        return torch.tensor(table, dtype=torch.int32).reshape(len(rows), width).to(self.device)
+
+    def context_lens(self, seq_ids: Sequence[Optional[Hashable]]) -> torch.Tensor:
+        """int32 ``[len(seq_ids)]``: tokens held per sequence (0 for ``None`` / unknown ids)."""
+        lens = [self._lens.get(s, 0) if s is not None else 0 for s in seq_ids]
+        return torch.tensor(lens, dtype=torch.int32).to(self.device)

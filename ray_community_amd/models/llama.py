@@ -15,6 +15,7 @@ GQA, XCD-grouped workgroup order); GEMMs are hipBLASLt via torch.
 """
 from __future__ import annotations
 
+import itertools
 import math
 from dataclasses import dataclass, field
 
@@ -95,9 +96,15 @@ class Attention(nn.Module):
     def forward(self, x, cs, B, S, positions=None):
         cfg = self.cfg
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
-        T = B * S
         qkv = self.qkv(x)  # [T, (Hq+2Hk)*D]
         qkv = ops.apply_rope_(qkv, cs, S, Hq, Hk, D, positions)
+        return self.causal_attention(qkv, B, S)
+
+    def causal_attention(self, qkv, B, S):
+        """Causal self-attention + output projection on the rotated fused ``qkv`` [B*S, W]."""
+        cfg = self.cfg
+        D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+        T = B * S
         if qkv.is_cuda and cfg.attn_impl == "hip" and ops.flash_attention_supported(S, D, Hq, Hk):
             # gfx950 flash attention straight off the fused projection; backward fills dqkv directly
             return self.o(ops.flash_attention_qkv(qkv, B, S, Hq, Hk, D, causal=True))
@@ -165,6 +172,7 @@ class Llama(nn.Module):
         return t
 
     def hidden_states(self, tokens, positions=None):
+        # the residual / norm chaining below is repeated in _run_layers (inference): keep them in step
         B, S = tokens.shape
         cs = self.rope_table(tokens.device)
         residual = self.embed(tokens).view(B * S, -1)
@@ -196,6 +204,174 @@ class Llama(nn.Module):
         if labels is None:
             return logits.view(*tokens.shape, -1)
         return ops.cross_entropy(logits, labels.reshape(-1), inplace_backward=True)
+
+    # ------------------------------------------------------------------------------ inference
+    # Generation over a paged KV cache (models/kv_cache.py). Under inference mode the fused-wgrad
+    # linears and the fused embedding are plain ``F.linear`` / ``F.embedding`` (their autograd
+    # paths are taken only when gradients are enabled), so the training modules are used as is.
+    def _run_layers(self, residual, attn):
+        """The layer stack of ``hidden_states`` with ``attn(i, blk, h)`` as the attention."""
+        h = self.layers[0].attn_norm(residual) if len(self.layers) else residual
+        for i, blk in enumerate(self.layers):
+            a = attn(i, blk, h)
+            h, residual = blk.mlp_norm(a, residual=residual)
+            m = blk.mlp(h)
+            nxt = self.layers[i + 1].attn_norm if i + 1 < len(self.layers) else self.norm
+            h, residual = nxt(m, residual=residual)
+        if not len(self.layers):
+            h = self.norm(residual)
+        return h
+
+    @torch.inference_mode()
+    def prefill(self, tokens, lengths, cache, seq_ids):
+        """Run the prompts through the model, fill ``cache`` and return the logits ``[B, V]`` of
+        each sequence's last real token.
+
+        ``tokens``: ``[B, S]`` right-padded token ids (or a list of token lists, then ``lengths``
+        may be ``None``); ``lengths``: real length per row. The batch is right-padded to a
+        multiple of 128 and run through the ordinary causal forward (right padding cannot reach a
+        real token through a causal mask); padded tokens get slot -1, i.e. are not cached."""
+        cfg = self.cfg
+        dev = self.embed.weight.device
+        if not torch.is_tensor(tokens):
+            rows = [list(r) for r in tokens]
+            lengths = [len(r) for r in rows] if lengths is None else lengths
+            width = max(len(r) for r in rows)
+            tokens = torch.tensor([r + [0] * (width - len(r)) for r in rows], dtype=torch.long)
+        lengths = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        B = tokens.shape[0]
+        if len(lengths) != B or len(seq_ids) != B:
+            raise ValueError("tokens, lengths and seq_ids must agree on the batch size")
+        if min(lengths) < 1 or max(lengths) > tokens.shape[1]:
+            raise ValueError("every prompt needs between 1 and tokens.shape[1] tokens")
+        S = -(-max(lengths) // 128) * 128
+        if S > cfg.max_seq_len:
+            raise ValueError(f"prompt of {max(lengths)} tokens pads to {S} > max_seq_len {cfg.max_seq_len}")
+        padded = torch.zeros(B, S, dtype=torch.long, device=dev)
+        keep = min(S, tokens.shape[1])
+        padded[:, :keep] = tokens[:, :keep].to(dev)
+        slots = torch.full((B, S), -1, dtype=torch.int32)
+        done = []
+        try:
+            for b, (sid, n) in enumerate(zip(seq_ids, lengths)):
+                slots[b, :n] = torch.tensor(cache.allocate(sid, n), dtype=torch.int32)
+                done.append(sid)
+        except Exception:
+            for sid in done:  # all or nothing
+                cache.free(sid)
+            raise
+        slots = slots.reshape(-1).to(dev)
+        cs = self.rope_table(dev)
+        D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+
+        def attn(i, blk, h):
+            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, S, Hq, Hk, D)
+            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
+            return blk.attn.causal_attention(qkv, B, S)
+
+        h = self._run_layers(self.embed(padded).view(B * S, -1), attn)
+        last = torch.tensor([b * S + n - 1 for b, n in enumerate(lengths)], dtype=torch.long, device=dev)
+        return self.logits(h[last])  # the B x S x V logits are never formed
+
+    @torch.inference_mode()
+    def decode_step(self, tokens, cache, seq_ids):
+        """One new token per sequence: append its K/V to ``cache`` and return logits ``[B, V]``.
+        A ``None`` in ``seq_ids`` is an inactive slot of a fixed-size batch (context length 0,
+        nothing cached; its logits row is meaningless)."""
+        cfg = self.cfg
+        dev = self.embed.weight.device
+        tokens = torch.as_tensor(tokens, dtype=torch.long).reshape(-1).to(dev)
+        B = tokens.shape[0]
+        if len(seq_ids) != B:
+            raise ValueError("tokens and seq_ids must agree on the batch size")
+        pos = [cache.length(s) if s is not None else 0 for s in seq_ids]
+        if max(pos) >= cfg.max_seq_len:
+            raise ValueError(f"sequence would exceed max_seq_len {cfg.max_seq_len}")
+        slots, done = [], []
+        try:
+            for s in seq_ids:
+                slots.append(cache.allocate(s, 1)[0] if s is not None else -1)
+                done.append(s)
+        except Exception:
+            for s in reversed(done):
+                if s is not None:  # give the one slot (and a block taken for it) back: all or nothing
+                    cache.rollback(s, 1)
+            raise
+        slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        positions = torch.tensor(pos, dtype=torch.int32, device=dev)
+        block_table, context_lens = cache.block_table(seq_ids), cache.context_lens(seq_ids)
+        cs = self.rope_table(dev)
+        D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+
+        def attn(i, blk, h):
+            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, 1, Hq, Hk, D, positions)
+            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
+            # q is read in place from the fused row
+            return blk.attn.o(ops.paged_attention_decode(qkv, cache.k[i], cache.v[i], block_table, context_lens,
+                                                         Hq, Hk, D))
+
+        return self.logits(self._run_layers(self.embed(tokens), attn))
+
+    @torch.inference_mode()
+    def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
+                 seed=None, cache=None):
+        """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
+        returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
+        (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
+        stops after emitting ``eos_token_id``. ``cache``: a ``PagedKVCache`` to use (its blocks are
+        released on exit); by default one just large enough is made."""
+        from .kv_cache import PagedKVCache
+
+        prompts = [list(p) for p in prompts]
+        if not prompts or max_new_tokens <= 0:
+            return [[] for _ in prompts]
+        dev = self.embed.weight.device
+        if max(len(p) for p in prompts) + max_new_tokens > self.cfg.max_seq_len:
+            raise ValueError(f"prompt + max_new_tokens exceeds max_seq_len {self.cfg.max_seq_len}")
+        if cache is None:
+            page = 16
+            blocks = sum(-(-(len(p) + max_new_tokens) // page) for p in prompts)
+            cache = PagedKVCache(self.cfg, blocks, page, device=dev, dtype=self.embed.weight.dtype)
+        gen = None
+        if temperature > 0:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(0 if seed is None else int(seed))
+        ids = [("generate", next(_SEQ_IDS)) for _ in prompts]
+        out = [[] for _ in prompts]
+        active = list(ids)
+        try:
+            logits = self.prefill(prompts, None, cache, ids)
+            for step in range(max_new_tokens):
+                nxt = sample_tokens(logits, temperature, top_k, gen).tolist()
+                for b, sid in enumerate(active):
+                    if sid is None:
+                        continue
+                    out[b].append(nxt[b])
+                    if eos_token_id is not None and nxt[b] == eos_token_id:
+                        cache.free(sid)
+                        active[b] = None
+                if step + 1 == max_new_tokens or all(s is None for s in active):
+                    break
+                logits = self.decode_step([t if s is not None else 0 for t, s in zip(nxt, active)], cache, active)
+        finally:
+            for sid in ids:
+                cache.free(sid)
+        return out
+
+
+_SEQ_IDS = itertools.count()
+
+
+def sample_tokens(logits, temperature: float = 0.0, top_k: int = 0, generator=None):
+    """Next token per row of ``logits`` [B, V]: argmax at ``temperature == 0``, else a sample of
+    softmax(logits / temperature) restricted to the ``top_k`` largest logits (0: all)."""
+    if temperature <= 0:
+        return logits.argmax(dim=-1)
+    x = logits.float() / float(temperature)
+    if top_k and top_k < x.shape[-1]:
+        kth = x.topk(int(top_k), dim=-1).values[:, -1:]
+        x = x.masked_fill(x < kth, float("-inf"))
+    return torch.multinomial(torch.softmax(x, dim=-1), 1, generator=generator).reshape(-1)
 
 
 def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, **overrides) -> Llama:

@@ -36,6 +36,9 @@ __all__ = [
     "flash_attention",
     "flash_attention_qkv",
     "flash_attention_supported",
+    "paged_decode_supported",
+    "kv_cache_append_",
+    "paged_attention_decode",
     "kernels_available",
 ]
 
@@ -1042,3 +1045,112 @@ def flash_attention(q, k, v, causal: bool = True, scale=None):
             and all(_token_major_ok(t) for t in (q, k, v))):
         return _FlashAttn.apply(q, k, v, causal, scale)
     return ref.attention_ref(q, k, v, causal, scale)
+
+
+# ------------------------------------------------------------------- paged KV cache / decode
+def paged_decode_supported(page_size: int, head_dim: int, n_q_heads: int, n_kv_heads: int) -> bool:
+    """Shapes the gfx950 cache-append and paged decode kernels cover (others use the reference)."""
+    return (page_size > 0 and page_size % 16 == 0 and head_dim in (64, 128) and n_kv_heads > 0
+            and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8))
+
+
+def _check_paged_caches(k_cache, v_cache, Hk, D):
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or tuple(k_cache.shape[2:]) != (Hk, D):
+        raise ValueError(f"k_cache / v_cache must both be [num_blocks, page_size, {Hk}, {D}], got "
+                         f"{tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    if k_cache.dtype != v_cache.dtype or k_cache.device != v_cache.device:
+        raise ValueError("k_cache and v_cache must share dtype and device")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("k_cache and v_cache must be contiguous")
+
+
+def _check_index(name, t, rows, device):
+    """An int32, contiguous index tensor on ``device`` whose first dimension is ``rows``."""
+    if t.dtype != torch.int32:
+        raise ValueError(f"{name} must be int32, got {t.dtype}")
+    if t.shape[0] != rows:
+        raise ValueError(f"{name} must have {rows} rows, got shape {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, expected {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: int):
+    """Write the K and V heads of every token of the fused, already rotated ``qkv``
+    ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]``, in place.
+
+    ``slot_mapping`` (int32 ``[T]``) gives each token's slot ``block * page_size + offset``; ``-1``
+    skips the token (padding). Slot values are not validated here (no device synchronisation):
+    they come from ``models.PagedKVCache``."""
+    _check_paged_caches(k_cache, v_cache, Hk, D)
+    W = (Hq + 2 * Hk) * D
+    if qkv.dim() != 2 or qkv.shape[1] != W or qkv.stride(1) != 1:
+        raise ValueError(f"qkv must be [T, {W}] with unit inner stride, got {tuple(qkv.shape)}")
+    if qkv.dtype != k_cache.dtype or qkv.device != k_cache.device:
+        raise ValueError("qkv and the caches must share dtype and device")
+    T = qkv.shape[0]
+    if slot_mapping.dim() != 1:
+        raise ValueError(f"slot_mapping must be 1-D, got shape {tuple(slot_mapping.shape)}")
+    _check_index("slot_mapping", slot_mapping, T, qkv.device)
+    page = k_cache.shape[1]
+    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
+            and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0):
+        check(lib().rca_kv_cache_append(qkv.data_ptr(), qkv.stride(0), slot_mapping.data_ptr(), k_cache.data_ptr(),
+                                        v_cache.data_ptr(), T, Hq, Hk, D, k_cache.shape[0] * page,
+                                        stream_ptr(qkv.device)), "rca_kv_cache_append")
+        return
+    ref.kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D)
+
+
+def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens, Hq: int, Hk: int, D: int,
+                           scale=None, num_splits=None):
+    """Single-token attention of ``B`` sequences over their paged KV caches. Returns ``[B, Hq*D]``.
+
+    ``q_or_qkv`` is ``[B, Hq*D]`` or the fused ``[B, (Hq+2Hk)*D]`` row, whose q heads are read in
+    place (any row stride). ``block_table`` (int32 ``[B, max_blocks]``) lists each sequence's
+    blocks in logical order; ``context_lens`` (int32 ``[B]``) its token count: tokens past it
+    never influence the result (whatever bytes their slots hold), and a length of 0 gives a zero
+    row. ``num_splits`` (default: ``rca_attn_decode_num_splits`` on ``max_blocks * page_size``)
+    splits each sequence's pages over that many workgroups, merged in a fixed order."""
+    _check_paged_caches(k_cache, v_cache, Hk, D)
+    if q_or_qkv.dim() != 2 or q_or_qkv.shape[1] not in (Hq * D, (Hq + 2 * Hk) * D) or q_or_qkv.stride(1) != 1:
+        raise ValueError(f"q must be [B, {Hq * D}] or the fused [B, {(Hq + 2 * Hk) * D}] row with unit inner "
+                         f"stride, got {tuple(q_or_qkv.shape)}")
+    if q_or_qkv.dtype != k_cache.dtype or q_or_qkv.device != k_cache.device:
+        raise ValueError("q and the caches must share dtype and device")
+    B = q_or_qkv.shape[0]
+    if block_table.dim() != 2 or block_table.shape[1] < 1:
+        raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(block_table.shape)}")
+    _check_index("block_table", block_table, B, q_or_qkv.device)
+    if context_lens.dim() != 1:
+        raise ValueError(f"context_lens must be 1-D, got shape {tuple(context_lens.shape)}")
+    _check_index("context_lens", context_lens, B, q_or_qkv.device)
+    if num_splits is not None and int(num_splits) < 1:
+        raise ValueError("num_splits must be >= 1")
+    scale = float(D ** -0.5 if scale is None else scale)
+    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
+    q = q_or_qkv
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
+            and q.stride(0) % 8 == 0 and q.data_ptr() % 16 == 0 and B <= 65535 and Hk <= 65535 and num_blocks > 0):
+        return ref.paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale)
+    out = torch.empty(B, Hq * D, device=q.device, dtype=q.dtype)
+    if B == 0:
+        return out
+    L = lib()
+    max_blocks = block_table.shape[1]
+    if num_splits is None:
+        num_splits = L.rca_attn_decode_num_splits(B, Hk, min(max_blocks * page, 2 ** 31 - 1), page)
+    num_splits = int(num_splits)
+    part_o = part_ml = None
+    if num_splits > 1:
+        # transient, stream-ordered workspaces (the caching allocator reuses them only for later
+        # work on this stream)
+        part_o = torch.empty(B, Hq, num_splits, D, device=q.device, dtype=torch.float32)
+        part_ml = torch.empty(B, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
+    check(L.rca_attn_decode_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                  block_table.data_ptr(), context_lens.data_ptr(), out.data_ptr(), _p(part_o),
+                                  _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale, num_splits,
+                                  stream_ptr(q.device)), "rca_attn_decode_paged")
+    del part_o, part_ml
+    return out

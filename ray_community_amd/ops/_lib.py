@@ -79,6 +79,10 @@ _SIGS = {
                               c_void_p]),
     "rca_image_normalize": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                      c_void_p]),
+    "rca_kv_cache_append": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_ll,
+                                    c_void_p]),
+    "rca_attn_decode_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 7 + [c_int] * 7 + [c_float, c_int, c_void_p]),
+    "rca_attn_decode_num_splits": (c_int, [c_int] * 4),
 }
 
 

@@ -158,3 +158,40 @@ def vtrace_ref(log_rhos, rewards, values, next_values, terminateds, dones, gamma
         vs[:, t] = v[:, t] + acc
         pg[:, t] = rpg[:, t] * (r[:, t] + disc[:, t] * vs_next - v[:, t])
     return vs, pg
+
+
+def kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D):
+    """Copy the K and V heads of each token of the fused (already rotated) ``qkv``
+    ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]`` at slot
+    ``slot_mapping[t]`` (= block * page_size + offset); ``-1`` skips the token. In place."""
+    T = qkv.shape[0]
+    keep = slot_mapping >= 0
+    slots = slot_mapping[keep].long()
+    k = qkv[:, Hq * D: (Hq + Hk) * D].reshape(T, Hk, D)[keep]
+    v = qkv[:, (Hq + Hk) * D: (Hq + 2 * Hk) * D].reshape(T, Hk, D)[keep]
+    k_cache.view(-1, Hk, D)[slots] = k.to(k_cache.dtype)
+    v_cache.view(-1, Hk, D)[slots] = v.to(v_cache.dtype)
+
+
+def paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale=None):
+    """fp32 single-token attention over a paged cache: per sequence, gather its pages through
+    ``block_table``, truncate to ``context_lens[b]`` tokens, softmax attention with GQA by head
+    repetition. ``q`` is ``[B, >= Hq*D]`` (the q heads lead a fused qkv row). Returns
+    ``[B, Hq*D]`` in ``q``'s dtype; a sequence of length 0 gives zeros."""
+    B = q.shape[0]
+    page = k_cache.shape[1]
+    scale = float(D ** -0.5 if scale is None else scale)
+    G = Hq // Hk
+    out = torch.zeros(B, Hq * D, dtype=torch.float32, device=q.device)
+    lens = context_lens.tolist()
+    for b in range(B):
+        n = int(lens[b])
+        if n <= 0:
+            continue
+        blocks = block_table[b, : (n + page - 1) // page].long()
+        k = k_cache[blocks].reshape(-1, Hk, D)[:n].float().repeat_interleave(G, dim=1)  # [n, Hq, D]
+        v = v_cache[blocks].reshape(-1, Hk, D)[:n].float().repeat_interleave(G, dim=1)
+        qb = q[b, : Hq * D].reshape(Hq, D).float()
+        p = torch.softmax(torch.einsum("hd,nhd->hn", qb, k) * scale, dim=-1)
+        out[b] = torch.einsum("hn,nhd->hd", p, v).reshape(Hq * D)
+    return out.to(q.dtype)

@@ -1,0 +1,118 @@
+"""Llama token streaming on Serve: one replica = one model + one continuous-batching engine.
+
+    app = LlamaDeployment.bind("llama3-1b", state_dict_path="/ckpt/model.pt", device="cuda")
+    handle = serve.run(app, route_prefix="/llm")
+    for tok in handle.options(method_name="generate", stream=True).remote([1, 2, 3], max_new_tokens=32):
+        ...
+
+Concurrent requests share the engine's decode batch (``models.GenerationEngine``): a background
+asyncio task steps the engine on a worker thread and hands every produced token to its request's
+queue, so tokens reach callers one by one. Token ids in, token ids out: no tokenizer.
+"""
+from __future__ import annotations
+
+import asyncio
+import concurrent.futures
+import json
+
+from .api import deployment
+
+
+class _LlamaDeployment:
+    def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
+                 num_blocks: int = 256, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16):
+        """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
+        ``torch.save``d state dict (without one the weights are initialised from ``seed``)."""
+        import torch
+
+        from ..models import GenerationEngine, build_llama
+
+        torch.manual_seed(seed)
+        self.model = build_llama(model, device=device, dtype=getattr(torch, dtype) if isinstance(dtype, str) else dtype)
+        if state_dict_path is not None:
+            self.model.load_state_dict(torch.load(state_dict_path, map_location=device))
+        self.model.eval()
+        self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size)
+        self.default_max_new_tokens = int(default_max_new_tokens)
+        # one model thread: the engine is not re-entrant, and per-thread GPU library state stays warm
+        self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="llama-engine")
+        # request id -> (queue, max_new_tokens, tokens routed so far). Entries are added on the engine
+        # thread (generate.add) and read / removed on the event loop: single dict operations, which the
+        # GIL makes atomic, and an entry is complete before its request can produce a token.
+        self._queues = {}
+        self._driver = None
+        self._cancelled = 0  # requests dropped because their consumer went away
+
+    async def _drive(self):
+        """Step the engine while it has work; route each token to its request's queue."""
+        loop = asyncio.get_running_loop()
+        try:
+            while self._queues or self.engine.has_work():
+                events = await loop.run_in_executor(self._exec, self.engine.step)
+                for rid, tok, finished in events:
+                    entry = self._queues.get(rid)
+                    if entry is not None:
+                        entry[2] += 1
+                        entry[0].put_nowait((tok, finished))
+                if not events:
+                    await asyncio.sleep(0.001)  # everything is waiting for cache blocks
+        except BaseException as e:  # a failed step fails every open stream instead of hanging it
+            for entry in self._queues.values():
+                entry[0].put_nowait(e)
+            raise
+        finally:
+            self._driver = None
+
+    async def generate(self, prompt_tokens, max_new_tokens=None, temperature: float = 0.0, top_k: int = 0,
+                       eos_token_id=None, seed=None):
+        """Async generator of the new token ids of one request."""
+        loop = asyncio.get_running_loop()
+        n = self.default_max_new_tokens if max_new_tokens is None else int(max_new_tokens)
+        q = asyncio.Queue()
+
+        def add():  # on the engine thread, so no step can run between queueing and registering
+            rid = self.engine.add_request(list(prompt_tokens), n, temperature=temperature, top_k=top_k,
+                                          eos_token_id=eos_token_id, seed=seed)
+            self._queues[rid] = [q, n, 0]
+            return rid
+
+        rid = await loop.run_in_executor(self._exec, add)
+        if self._driver is None:
+            self._driver = asyncio.ensure_future(self._drive())
+        finished = False
+        try:
+            while not finished:
+                item = await q.get()
+                if isinstance(item, BaseException):
+                    finished = True  # the engine failed: nothing left to cancel
+                    raise RuntimeError(f"generation failed: {item!r}")
+                tok, finished = item
+                yield tok
+        finally:
+            del self._queues[rid]
+            if not finished:  # the consumer went away: give the slot and the cache blocks back
+                self._cancelled += 1
+                loop.run_in_executor(self._exec, self.engine.cancel, rid)
+
+    async def status(self):
+        """Engine occupancy and, per open stream, how far it is: ``{"active", "waiting", "streams":
+        [{"request_id", "max_new_tokens", "produced"}], "cancelled"}``."""
+        streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
+                   for rid, e in list(self._queues.items())]
+        return {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
+                "cancelled": self._cancelled}
+
+    async def __call__(self, request):
+        """HTTP: JSON body ``{"prompt_tokens": [...], "max_new_tokens": n}`` (optionally
+        ``temperature``, ``top_k``, ``eos_token_id``, ``seed``) -> newline-delimited token ids."""
+        body = json.loads(await request.body())
+        kw = {k: body[k] for k in ("max_new_tokens", "temperature", "top_k", "eos_token_id", "seed") if k in body}
+
+        async def lines():
+            async for tok in self.generate(body["prompt_tokens"], **kw):
+                yield f"{tok}\n"
+
+        return lines()
+
+
+LlamaDeployment = deployment(_LlamaDeployment, name="LlamaDeployment")
