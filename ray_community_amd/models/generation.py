@@ -4,6 +4,12 @@
 runs one ``decode_step`` over all slots (inactive slots ride along at context length 0) and
 retires finished sequences, freeing their blocks. Pure Python over ``PagedKVCache`` and the
 ``Llama`` inference methods; it runs on whatever device the model is on.
+
+With ``prefill_chunk`` set, an admitted request is *prefilling*: every step feeds at most that
+many prompt tokens (arrival order, one ``Llama.extend`` call) before the decode step, so a long
+prompt no longer stalls the running streams for its whole prefill. ``register_prefix`` keeps a
+prompt prefix in a pinned sequence whose whole pages later requests share (``PagedKVCache.fork``)
+instead of recomputing and storing them again.
 """
 from __future__ import annotations
 
@@ -30,12 +36,39 @@ class _Request:
     produced: int = 0
     last: int = 0                    # last emitted token (the next decode input)
     seq_id: tuple = field(default=())
+    # chunked prefill / shared prefix (models.Llama.extend); unused on the plain prefill path
+    feed: List[int] = field(default_factory=list)   # tokens to run through extend
+    fed: int = 0                                    # ... of which this many are cached
+    prefilling: bool = False
+    prefix: Optional["_Prefix"] = None              # held until the prefill is over
+    forked: bool = False
+    shared: int = 0                                 # blocks shared with the prefix (not in ``blocks``)
+
+
+@dataclass
+class _Prefix:
+    handle: int
+    tokens: List[int]
+    seq_id: tuple
+    blocks: int
+    fed: int = 0
+    users: int = 0           # requests accepted with this prefix whose prefill is not over
+    reserved: bool = False   # its blocks are counted in the admission budget
+    released: bool = False
+
+
+_NO_LIMIT = 1 << 62
 
 
 class GenerationEngine:
     def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8, num_blocks: int = 256,
-                 page_size: int = 16):
+                 page_size: int = 16, prefill_chunk: Optional[int] = None):
         from .llama import sample_tokens
+
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("prefill_chunk must be >= 1")
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
+        self._prefixes = {}
 
         self.model = model
         w = model.embed.weight
@@ -47,30 +80,82 @@ class GenerationEngine:
         self._sample = sample_tokens
 
     # -------------------------------------------------------------------------------- requests
+    def register_prefix(self, tokens) -> int:
+        """Register a prompt prefix (system prompt, few-shot header) that requests can share;
+        returns its handle. The prefix is prefilled once into a pinned sequence, lazily, by the
+        first ``step()`` that needs it and through the same ``prefill_chunk`` budget."""
+        tokens = [int(t) for t in tokens]
+        if not tokens:
+            raise ValueError("a prefix needs at least one token")
+        if len(tokens) >= self.model.cfg.max_seq_len:
+            raise ValueError(f"prefix of {len(tokens)} tokens leaves no room under max_seq_len "
+                             f"{self.model.cfg.max_seq_len}")
+        handle = next(self._ids)
+        self._prefixes[handle] = _Prefix(handle, tokens, ("engine-prefix", id(self), handle),
+                                         -(-len(tokens) // self.cache.page_size))
+        return handle
+
+    def release_prefix(self, handle: int) -> None:
+        """Unpin a prefix: no new request may name it, and its blocks go back once the last
+        request sharing them retires."""
+        pfx = self._prefixes.pop(handle, None)
+        if pfx is None:
+            raise ValueError(f"unknown or released prefix handle {handle!r}")
+        pfx.released = True
+        self._drop_prefix_if_unused(pfx)
+
+    def _drop_prefix_if_unused(self, pfx: "_Prefix"):
+        if pfx.released and pfx.users == 0:
+            self.cache.free(pfx.seq_id)  # shared pages live on until their last sharer retires
+            pfx.fed, pfx.reserved = 0, False
+
+    def _unhold_prefix(self, req: "_Request"):
+        if req.prefix is not None:
+            pfx, req.prefix = req.prefix, None
+            pfx.users -= 1
+            self._drop_prefix_if_unused(pfx)
+
     def add_request(self, prompt, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
-                    seed=None) -> int:
+                    seed=None, prefix: Optional[int] = None) -> int:
         """Queue a request; returns its id. It is admitted by a later ``step()`` once a slot is
-        free and the cache can hold its whole sequence (prompt + ``max_new_tokens``)."""
+        free and the cache can hold its whole sequence (prompt + ``max_new_tokens``). With
+        ``prefix`` (a ``register_prefix`` handle) ``prompt`` is the suffix after that prefix: the
+        request shares the prefix's whole cache pages and needs blocks only for the rest."""
         prompt = [int(t) for t in prompt]
         if not prompt or max_new_tokens < 1:
             raise ValueError("a request needs a non-empty prompt and max_new_tokens >= 1")
-        total = len(prompt) + int(max_new_tokens)
+        pfx = None
+        if prefix is not None:
+            pfx = self._prefixes.get(prefix)
+            if pfx is None:
+                raise ValueError(f"unknown or released prefix handle {prefix!r}")
+        page = self.cache.page_size
+        whole = len(pfx.tokens) // page * page if pfx is not None else 0
+        total = (len(pfx.tokens) if pfx is not None else 0) + len(prompt) + int(max_new_tokens)
         if total > self.model.cfg.max_seq_len:
             raise ValueError(f"prompt + max_new_tokens = {total} exceeds max_seq_len {self.model.cfg.max_seq_len}")
-        padded = -(-len(prompt) // 128) * 128  # what prefill pads the prompt to
-        if padded > self.model.cfg.max_seq_len:
-            raise ValueError(f"prompt of {len(prompt)} tokens pads to {padded} > max_seq_len "
-                             f"{self.model.cfg.max_seq_len}")
-        blocks = -(-total // self.cache.page_size)
-        if blocks > self.cache.num_blocks:
+        if self.prefill_chunk is None and pfx is None:
+            padded = -(-len(prompt) // 128) * 128  # what prefill pads the prompt to
+            if padded > self.model.cfg.max_seq_len:
+                raise ValueError(f"prompt of {len(prompt)} tokens pads to {padded} > max_seq_len "
+                                 f"{self.model.cfg.max_seq_len}")
+        blocks = -(-total // page) - whole // page  # shared pages are the prefix's, not the request's
+        if blocks + (pfx.blocks if pfx is not None else 0) > self.cache.num_blocks:
             raise ValueError(f"request needs {blocks} cache blocks, the cache has {self.cache.num_blocks}")
         gen = None
         if temperature > 0:
             gen = torch.Generator(device=self.model.embed.weight.device)
             gen.manual_seed(0 if seed is None else int(seed))
         rid = next(self._ids)
-        self.waiting.append(_Request(rid, prompt, int(max_new_tokens), float(temperature), int(top_k), eos_token_id,
-                                     gen, blocks, seq_id=("engine", id(self), rid)))
+        req = _Request(rid, prompt, int(max_new_tokens), float(temperature), int(top_k), eos_token_id, gen, blocks,
+                       seq_id=("engine", id(self), rid))
+        if pfx is not None:
+            req.prefix = pfx
+            pfx.users += 1
+            req.feed = pfx.tokens[whole:] + prompt  # the partly filled page is recomputed per request
+        else:
+            req.feed = prompt
+        self.waiting.append(req)
         return rid
 
     def cancel(self, request_id: int) -> bool:
@@ -79,6 +164,7 @@ class GenerationEngine:
         for req in self.waiting:
             if req.rid == request_id:
                 self.waiting.remove(req)
+                self._unhold_prefix(req)
                 return True
         for slot, req in enumerate(self.slots):
             if req is not None and req.rid == request_id:
@@ -93,9 +179,16 @@ class GenerationEngine:
     def num_active(self) -> int:
         return sum(r is not None for r in self.slots)
 
+    @property
+    def num_prefilling(self) -> int:
+        return sum(r is not None and r.prefilling for r in self.slots)
+
     def _reserved(self) -> int:
-        """Blocks the active requests may still take while they decode."""
-        return sum(r.blocks - self.cache.blocks_held(r.seq_id) for r in self.slots if r is not None)
+        """Blocks the active requests (and the prefixes they wait for) may still take."""
+        own = sum(r.blocks + r.shared - self.cache.blocks_held(r.seq_id) for r in self.slots if r is not None)
+        pfx = {id(r.prefix): r.prefix for r in list(self.slots) + list(self.waiting)
+               if r is not None and r.prefix is not None and r.prefix.reserved}
+        return own + sum(p.blocks - self.cache.blocks_held(p.seq_id) for p in pfx.values())
 
     # ------------------------------------------------------------------------------------ step
     def _emit(self, req: _Request, logits_row, events) -> bool:
@@ -107,8 +200,68 @@ class GenerationEngine:
         return finished
 
     def _retire(self, slot: int):
-        self.cache.free(self.slots[slot].seq_id)
+        req = self.slots[slot]
+        self.cache.free(req.seq_id)
+        self._unhold_prefix(req)
         self.slots[slot] = None
+
+    def _requeue(self, slots):
+        """Back to the head of the queue, in arrival order, with nothing cached."""
+        for slot in sorted(slots, key=lambda s: self.slots[s].rid, reverse=True):
+            req = self.slots[slot]
+            self.cache.free(req.seq_id)
+            req.fed, req.prefilling, req.forked, req.shared = 0, False, False, 0
+            self.waiting.appendleft(req)
+            self.slots[slot] = None
+
+    def _extend_prefilling(self, events):
+        """Feed up to ``prefill_chunk`` prompt tokens of the prefilling requests, in arrival order
+        and in one ``extend`` call. A request whose prefix is not cached yet waits while the
+        prefix takes its turn. Returns the ids of the requests that finished their prompt."""
+        pre = sorted((s for s, r in enumerate(self.slots) if r is not None and r.prefilling),
+                     key=lambda s: self.slots[s].rid)
+        budget = self.prefill_chunk if self.prefill_chunk is not None else _NO_LIMIT
+        items, busy = [], set()  # (slot or None, request or prefix, tokens)
+        for slot in pre:
+            if budget <= 0:
+                break
+            req = self.slots[slot]
+            pfx = req.prefix
+            if pfx is not None and not req.forked:
+                if pfx.fed < len(pfx.tokens):
+                    if pfx.handle not in busy:
+                        n = min(budget, len(pfx.tokens) - pfx.fed)
+                        items.append((None, pfx, pfx.tokens[pfx.fed: pfx.fed + n]))
+                        busy.add(pfx.handle)
+                        budget -= n
+                    continue
+                whole = len(pfx.tokens) // self.cache.page_size * self.cache.page_size
+                self.cache.fork(pfx.seq_id, req.seq_id, whole)
+                req.forked, req.shared = True, whole // self.cache.page_size
+            n = min(budget, len(req.feed) - req.fed)
+            items.append((slot, req, req.feed[req.fed: req.fed + n]))
+            budget -= n
+        joined = set()
+        if not items:
+            return joined
+        try:
+            logits = self.model.extend([t for _, _, t in items], self.cache, [o.seq_id for _, o, _ in items])
+        except Exception:
+            # extend cached nothing (it is all or nothing): its requests go back to the head of the
+            # queue in arrival order, so no slot decodes a sequence that was never prefilled
+            self._requeue([slot for slot, _, _ in items if slot is not None])
+            raise
+        for i, (slot, obj, toks) in enumerate(items):
+            obj.fed += len(toks)
+            if slot is None or obj.fed < len(obj.feed):
+                continue
+            obj.prefilling = False
+            self._unhold_prefix(obj)
+            if self._emit(obj, logits[i], events):
+                self._retire(slot)
+            else:
+                joined.add(obj.rid)  # decodes from the next step on
+        return joined
 
     def step(self) -> List[Tuple[int, int, bool]]:
         """Admit, prefill, decode once, retire. Returns ``(request_id, token, finished)`` for every
@@ -117,12 +270,22 @@ class GenerationEngine:
         # admit in arrival order: a request that does not fit waits (and keeps its place)
         admitted = []
         budget = self.cache.num_free_blocks - self._reserved()
-        while self.waiting and None in self.slots and self.waiting[0].blocks <= budget:
-            req = self.waiting.popleft()
-            budget -= req.blocks
+        while self.waiting and None in self.slots:
+            req = self.waiting[0]
+            pfx = req.prefix if req.prefix is not None and not req.prefix.reserved else None
+            need = req.blocks + (pfx.blocks if pfx is not None else 0)
+            if need > budget:
+                break
+            self.waiting.popleft()
+            budget -= need
+            if pfx is not None:
+                pfx.reserved = True
             slot = self.slots.index(None)
             self.slots[slot] = req
-            admitted.append(slot)
+            if self.prefill_chunk is None and req.prefix is None:
+                admitted.append(slot)  # the plain path: one prefill, below
+            else:
+                req.prefilling = True
         if admitted:
             reqs = [self.slots[s] for s in admitted]
             try:
@@ -137,11 +300,14 @@ class GenerationEngine:
             for i, slot in enumerate(admitted):
                 if self._emit(self.slots[slot], logits[i], events):
                     self._retire(slot)
-        if any(r is not None for r in self.slots):
-            seq_ids = [r.seq_id if r is not None else None for r in self.slots]
-            tokens = [r.last if r is not None else 0 for r in self.slots]
+        joined = self._extend_prefilling(events)
+        # requests still in their prompt, or that left it in this step, ride along as inactive slots
+        live = [r is not None and not r.prefilling and r.rid not in joined for r in self.slots]
+        if any(live):
+            seq_ids = [r.seq_id if on else None for r, on in zip(self.slots, live)]
+            tokens = [r.last if on else 0 for r, on in zip(self.slots, live)]
             logits = self.model.decode_step(tokens, self.cache, seq_ids)
             for slot, req in enumerate(self.slots):
-                if req is not None and self._emit(req, logits[slot], events):
+                if live[slot] and self._emit(req, logits[slot], events):
                     self._retire(slot)
         return events

@@ -3,7 +3,10 @@
 Per layer the cache is two tensors ``[num_blocks, page_size, Hk, D]``; a sequence owns a list of
 blocks (in logical order) and token ``i`` of it lives in slot ``blocks[i // page_size] * page_size
 + i % page_size``. Every block id and slot handed to the kernels (``ops.kv_cache_append_``,
-``ops.paged_attention_decode``) comes from this allocator, which is what keeps them in range.
+``ops.paged_attention_decode``, ``ops.paged_attention_extend``) comes from this allocator, which
+is what keeps them in range. ``fork`` lets a new sequence share the whole leading pages of another
+(a common prompt prefix): blocks carry a reference count and return to the free list when their
+last owner lets go.
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ class PagedKVCache:
         self._free: List[int] = list(range(self.num_blocks - 1, -1, -1))  # stack: block 0 goes first
         self._blocks: Dict[Hashable, List[int]] = {}
         self._lens: Dict[Hashable, int] = {}
+        self._refs: List[int] = [0] * self.num_blocks  # owners per block (> 1 only after fork)
 
     @property
     def num_free_blocks(self) -> int:
@@ -53,21 +57,54 @@ class PagedKVCache:
                               f"{len(self._free)} of {self.num_blocks} free")
         blocks = self._blocks.setdefault(seq_id, [])
         for _ in range(need):
-            blocks.append(self._free.pop())
+            blk = self._free.pop()
+            self._refs[blk] = 1
+            blocks.append(blk)
         start = self._lens.get(seq_id, 0)
         self._lens[seq_id] = start + int(n_tokens)
         P = self.page_size
         return [blocks[i // P] * P + i % P for i in range(start, start + int(n_tokens))]
 
     def free(self, seq_id) -> None:
-        """Return the blocks of ``seq_id`` to the free list (unknown ids are ignored)."""
-        self._free.extend(reversed(self._blocks.pop(seq_id, [])))
+        """Give up the blocks of ``seq_id`` (unknown ids are ignored): each goes back to the free
+        list unless a forked sequence still shares it."""
+        for blk in reversed(self._blocks.pop(seq_id, [])):
+            self._release(blk)
         self._lens.pop(seq_id, None)
+
+    def _release(self, blk: int) -> None:
+        self._refs[blk] -= 1
+        if self._refs[blk] == 0:
+            self._free.append(blk)
+
+    def fork(self, parent_id, child_id, n_tokens: int) -> None:
+        """Start ``child_id`` as a sequence of ``n_tokens`` tokens sharing the first
+        ``n_tokens / page_size`` blocks of ``parent_id`` (no copy). ``n_tokens`` must be a multiple
+        of ``page_size`` (a partly filled shared page would be written by two owners) and at most
+        the parent's length, and ``child_id`` must be unused; otherwise ``ValueError`` and nothing
+        changes. Either sequence may be freed or rolled back first."""
+        n_tokens = int(n_tokens)
+        if child_id in self._blocks or child_id in self._lens:
+            raise ValueError(f"sequence {child_id!r} already exists")
+        if parent_id not in self._lens:
+            raise ValueError(f"unknown parent sequence {parent_id!r}")
+        if n_tokens < 0 or n_tokens % self.page_size:
+            raise ValueError(f"n_tokens must be a non-negative multiple of page_size {self.page_size}, got {n_tokens}")
+        if n_tokens > self._lens[parent_id]:
+            raise ValueError(f"cannot share {n_tokens} tokens of sequence {parent_id!r}, which holds "
+                             f"{self._lens[parent_id]}")
+        if n_tokens == 0:
+            return  # nothing shared: the child is created by its first allocate
+        shared = self._blocks[parent_id][: n_tokens // self.page_size]
+        for blk in shared:
+            self._refs[blk] += 1
+        self._blocks[child_id] = list(shared)
+        self._lens[child_id] = n_tokens
 
     def rollback(self, seq_id, n_tokens: int) -> None:
         """Undo the last ``n_tokens`` of ``seq_id``: blocks they alone occupied go back to the free
-        list (in the order ``allocate`` would hand them out again), and a sequence left with no
-        tokens is forgotten."""
+        list (in the order ``allocate`` would hand them out again) unless a forked sequence still
+        shares them, and a sequence left with no tokens is forgotten."""
         have = self._lens.get(seq_id, 0)
         if n_tokens < 0 or n_tokens > have:
             raise ValueError(f"cannot roll back {n_tokens} of {have} tokens of sequence {seq_id!r}")
@@ -75,7 +112,7 @@ class PagedKVCache:
         blocks = self._blocks.get(seq_id, [])
         keep = -(-left // self.page_size)
         while len(blocks) > keep:
-            self._free.append(blocks.pop())
+            self._release(blocks.pop())
         if left == 0:
             self._blocks.pop(seq_id, None)
             self._lens.pop(seq_id, None)

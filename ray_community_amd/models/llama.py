@@ -313,14 +313,73 @@ class Llama(nn.Module):
         return self.logits(self._run_layers(self.embed(tokens), attn))
 
     @torch.inference_mode()
+    def extend(self, tokens, cache, seq_ids):
+        """Append several new tokens to each sequence and return the logits ``[B, V]`` of each
+        sequence's last new token.
+
+        ``tokens`` is a list of non-empty token lists; each ``seq_id`` may be new or already cached
+        at any length (a prompt chunk, a further chat turn, draft tokens to verify). The batch is
+        packed ragged (``sum(len)`` rows, no padding) and attends through
+        ``ops.paged_attention_extend`` over the cache, which already holds the new tokens' K/V by
+        then. Allocation is all or nothing: on ``KVCacheFull`` the cache is what it was."""
+        cfg = self.cfg
+        dev = self.embed.weight.device
+        rows = [[int(t) for t in r] for r in tokens]
+        B = len(rows)
+        if len(seq_ids) != B:
+            raise ValueError("tokens and seq_ids must agree on the batch size")
+        if B == 0 or min(len(r) for r in rows) < 1:
+            raise ValueError("extend needs at least one sequence and at least one new token per sequence")
+        if len(set(seq_ids)) != B:
+            raise ValueError("a sequence may appear once per extend call")
+        start = [cache.length(s) for s in seq_ids]
+        if max(p + len(r) for p, r in zip(start, rows)) > cfg.max_seq_len:
+            raise ValueError(f"sequence would exceed max_seq_len {cfg.max_seq_len}")
+        slots, done = [], []
+        try:
+            for s, r in zip(seq_ids, rows):
+                slots.extend(cache.allocate(s, len(r)))
+                done.append((s, len(r)))
+        except Exception:
+            for s, n in reversed(done):  # all or nothing
+                cache.rollback(s, n)
+            raise
+        flat = torch.tensor([t for r in rows for t in r], dtype=torch.long, device=dev)
+        slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        positions = torch.tensor([p + i for p, r in zip(start, rows) for i in range(len(r))], dtype=torch.int32,
+                                 device=dev)
+        cu = list(itertools.accumulate([len(r) for r in rows], initial=0))
+        cu_q_lens = torch.tensor(cu, dtype=torch.int32, device=dev)
+        max_q_len = max(len(r) for r in rows)
+        block_table, context_lens = cache.block_table(seq_ids), cache.context_lens(seq_ids)
+        cs = self.rope_table(dev)
+        D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+
+        def attn(i, blk, h):
+            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, 1, Hq, Hk, D, positions)
+            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
+            # q is read in place from the fused rows
+            return blk.attn.o(ops.paged_attention_extend(qkv, cache.k[i], cache.v[i], block_table, context_lens,
+                                                         cu_q_lens, max_q_len, Hq, Hk, D))
+
+        h = self._run_layers(self.embed(flat), attn)
+        last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.long, device=dev)
+        return self.logits(h[last])
+
+    @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
-                 seed=None, cache=None):
+                 seed=None, cache=None, prefill_chunk=None):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
         stops after emitting ``eos_token_id``. ``cache``: a ``PagedKVCache`` to use (its blocks are
-        released on exit); by default one just large enough is made."""
+        released on exit); by default one just large enough is made. ``prefill_chunk``: feed the
+        prompts through ``extend``, at most that many tokens per sequence per call, instead of
+        one ``prefill``."""
         from .kv_cache import PagedKVCache
+
+        if prefill_chunk is not None and int(prefill_chunk) < 1:
+            raise ValueError("prefill_chunk must be >= 1")
 
         prompts = [list(p) for p in prompts]
         if not prompts or max_new_tokens <= 0:
@@ -340,7 +399,10 @@ class Llama(nn.Module):
         out = [[] for _ in prompts]
         active = list(ids)
         try:
-            logits = self.prefill(prompts, None, cache, ids)
+            if prefill_chunk is None:
+                logits = self.prefill(prompts, None, cache, ids)
+            else:
+                logits = self._chunked_prefill(prompts, cache, ids, int(prefill_chunk))
             for step in range(max_new_tokens):
                 nxt = sample_tokens(logits, temperature, top_k, gen).tolist()
                 for b, sid in enumerate(active):
@@ -357,6 +419,18 @@ class Llama(nn.Module):
             for sid in ids:
                 cache.free(sid)
         return out
+
+
+    def _chunked_prefill(self, prompts, cache, ids, chunk):
+        """``prefill`` through ``extend``: ``chunk`` tokens per unfinished prompt per call."""
+        logits = [None] * len(prompts)
+        for off in range(0, max(len(p) for p in prompts), chunk):
+            idx = [b for b, p in enumerate(prompts) if off < len(p)]
+            lg = self.extend([prompts[b][off: off + chunk] for b in idx], cache, [ids[b] for b in idx])
+            for j, b in enumerate(idx):
+                if off + chunk >= len(prompts[b]):
+                    logits[b] = lg[j]
+        return torch.stack(logits)
 
 
 _SEQ_IDS = itertools.count()

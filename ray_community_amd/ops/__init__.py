@@ -39,6 +39,7 @@ __all__ = [
     "paged_decode_supported",
     "kv_cache_append_",
     "paged_attention_decode",
+    "paged_attention_extend",
     "kernels_available",
 ]
 
@@ -1153,4 +1154,56 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
                                   _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale, num_splits,
                                   stream_ptr(q.device)), "rca_attn_decode_paged")
     del part_o, part_ml
+    return out
+
+
+def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens, cu_q_lens, max_q_len: int, Hq: int,
+                           Hk: int, D: int, scale=None):
+    """Causal attention of a ragged batch of query chunks over their paged KV caches, each chunk
+    at the end of its sequence's context. Returns ``[T, Hq*D]``.
+
+    ``q_or_qkv`` is the packed ``[T, Hq*D]`` or the fused ``[T, (Hq+2Hk)*D]`` rows, whose q heads
+    are read in place (any row stride). Sequence ``b`` owns rows ``cu_q_lens[b] ..
+    cu_q_lens[b+1]-1`` (int32 ``[B+1]``, non-decreasing, at most ``T``; a sequence may own none);
+    ``context_lens[b]`` (int32 ``[B]``) counts its cached tokens INCLUDING these rows, whose K/V
+    must already be in the cache, so row ``i`` of the chunk sits at position ``context_lens[b] -
+    n_b + i`` and attends keys ``0 .. position`` through ``block_table`` (int32 ``[B,
+    max_blocks]``). Tokens past a context length never influence the result. ``max_q_len`` is an
+    upper bound on the chunk lengths known on the host (it sizes the launch: no device
+    synchronisation here; longer chunks are cut to it); rows no sequence owns are undefined."""
+    _check_paged_caches(k_cache, v_cache, Hk, D)
+    if q_or_qkv.dim() != 2 or q_or_qkv.shape[1] not in (Hq * D, (Hq + 2 * Hk) * D) or q_or_qkv.stride(1) != 1:
+        raise ValueError(f"q must be [T, {Hq * D}] or the fused [T, {(Hq + 2 * Hk) * D}] row with unit inner "
+                         f"stride, got {tuple(q_or_qkv.shape)}")
+    if q_or_qkv.dtype != k_cache.dtype or q_or_qkv.device != k_cache.device:
+        raise ValueError("q and the caches must share dtype and device")
+    T = q_or_qkv.shape[0]
+    if context_lens.dim() != 1:
+        raise ValueError(f"context_lens must be 1-D, got shape {tuple(context_lens.shape)}")
+    B = context_lens.shape[0]
+    _check_index("context_lens", context_lens, B, q_or_qkv.device)
+    if block_table.dim() != 2 or block_table.shape[1] < 1:
+        raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(block_table.shape)}")
+    _check_index("block_table", block_table, B, q_or_qkv.device)
+    if cu_q_lens.dim() != 1:
+        raise ValueError(f"cu_q_lens must be 1-D, got shape {tuple(cu_q_lens.shape)}")
+    _check_index("cu_q_lens", cu_q_lens, B + 1, q_or_qkv.device)
+    max_q_len = int(max_q_len)
+    if max_q_len < 0 or max_q_len > T:
+        raise ValueError(f"max_q_len must be between 0 and T = {T}, got {max_q_len}")
+    scale = float(D ** -0.5 if scale is None else scale)
+    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
+    q = q_or_qkv
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
+            and q.stride(0) % 8 == 0 and q.data_ptr() % 16 == 0 and B <= 65535 and Hk <= 65535 and num_blocks > 0
+            and num_blocks * page < 2 ** 31 and scale > 0):
+        return ref.paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, cu_q_lens, Hq, Hk, D,
+                                              scale)
+    out = torch.empty(T, Hq * D, device=q.device, dtype=q.dtype)
+    if T == 0 or B == 0 or max_q_len == 0:
+        return out
+    check(lib().rca_attn_extend_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                      block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
+                                      out.data_ptr(), B, max_q_len, Hq, Hk, D, page, block_table.shape[1], num_blocks,
+                                      scale, stream_ptr(q.device)), "rca_attn_extend_paged")
     return out

@@ -195,3 +195,35 @@ def paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, H
         p = torch.softmax(torch.einsum("hd,nhd->hn", qb, k) * scale, dim=-1)
         out[b] = torch.einsum("hn,nhd->hd", p, v).reshape(Hq * D)
     return out.to(q.dtype)
+
+
+def paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, cu_q_lens, Hq, Hk, D, scale=None):
+    """fp32 causal attention of a ragged batch of query chunks over a paged cache. Sequence ``b``
+    owns rows ``cu_q_lens[b] .. cu_q_lens[b+1]-1`` of ``q`` (``[T, >= Hq*D]``); ``context_lens[b]``
+    counts its cached tokens including these ``n_b``, so query ``i`` sits at position
+    ``context_lens[b] - n_b + i`` and attends keys ``0 .. position``, gathered through
+    ``block_table``. Returns ``[T, Hq*D]`` in ``q``'s dtype; a sequence with ``n_b = 0``
+    contributes no rows, and rows no sequence owns are zero."""
+    T = q.shape[0]
+    page = k_cache.shape[1]
+    scale = float(D ** -0.5 if scale is None else scale)
+    G = Hq // Hk
+    out = torch.zeros(T, Hq * D, dtype=torch.float32, device=q.device)
+    lens = context_lens.tolist()
+    cu = cu_q_lens.tolist()
+    for b in range(len(lens)):
+        q0, q1 = int(cu[b]), int(cu[b + 1])
+        n, ctx = q1 - q0, int(lens[b])
+        if n <= 0 or ctx <= 0:
+            continue
+        blocks = block_table[b, : (ctx + page - 1) // page].long()
+        k = k_cache[blocks].reshape(-1, Hk, D)[:ctx].float().repeat_interleave(G, dim=1)  # [ctx, Hq, D]
+        v = v_cache[blocks].reshape(-1, Hk, D)[:ctx].float().repeat_interleave(G, dim=1)
+        qb = q[q0:q1, : Hq * D].reshape(n, Hq, D).float()
+        s = torch.einsum("ihd,nhd->hin", qb, k) * scale
+        pos = torch.arange(ctx - n, ctx, device=q.device)
+        hidden = torch.arange(ctx, device=q.device)[None, :] > pos[:, None]  # [n, ctx]
+        p = torch.softmax(s.masked_fill(hidden[None], float("-inf")), dim=-1)
+        p = torch.nan_to_num(p)  # a query before position 0 sees nothing: zeros
+        out[q0:q1] = torch.einsum("hin,nhd->ihd", p, v).reshape(n, Hq * D)
+    return out.to(q.dtype)

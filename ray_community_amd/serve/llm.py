@@ -20,9 +20,12 @@ from .api import deployment
 
 class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
-                 num_blocks: int = 256, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16):
+                 num_blocks: int = 256, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
+                 prefill_chunk=None):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
-        ``torch.save``d state dict (without one the weights are initialised from ``seed``)."""
+        ``torch.save``d state dict (without one the weights are initialised from ``seed``);
+        ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
+        no longer pauses the running streams for its whole prefill); ``None`` prefills in one go."""
         import torch
 
         from ..models import GenerationEngine, build_llama
@@ -32,7 +35,8 @@ class _LlamaDeployment:
         if state_dict_path is not None:
             self.model.load_state_dict(torch.load(state_dict_path, map_location=device))
         self.model.eval()
-        self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size)
+        self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
+                                       prefill_chunk=prefill_chunk)
         self.default_max_new_tokens = int(default_max_new_tokens)
         # one model thread: the engine is not re-entrant, and per-thread GPU library state stays warm
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="llama-engine")
@@ -54,7 +58,7 @@ class _LlamaDeployment:
                     if entry is not None:
                         entry[2] += 1
                         entry[0].put_nowait((tok, finished))
-                if not events:
+                if not events and not self.engine.num_prefilling:
                     await asyncio.sleep(0.001)  # everything is waiting for cache blocks
         except BaseException as e:  # a failed step fails every open stream instead of hanging it
             for entry in self._queues.values():
@@ -96,11 +100,16 @@ class _LlamaDeployment:
 
     async def status(self):
         """Engine occupancy and, per open stream, how far it is: ``{"active", "waiting", "streams":
-        [{"request_id", "max_new_tokens", "produced"}], "cancelled"}``."""
+        [{"request_id", "max_new_tokens", "produced"}], "cancelled"}``; a deployment with
+        ``prefill_chunk`` set adds ``"prefill_chunk"`` and ``"prefilling"`` (requests still in
+        their prompt)."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
                    for rid, e in list(self._queues.items())]
-        return {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
-                "cancelled": self._cancelled}
+        st = {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
+              "cancelled": self._cancelled}
+        if self.engine.prefill_chunk is not None:
+            st.update(prefill_chunk=self.engine.prefill_chunk, prefilling=self.engine.num_prefilling)
+        return st
 
     async def __call__(self, request):
         """HTTP: JSON body ``{"prompt_tokens": [...], "max_new_tokens": n}`` (optionally
