@@ -21,6 +21,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from .kv_cache import PagedKVCache
+from .llama import _seeded_generator, sample_tokens
 
 
 @dataclass
@@ -63,13 +64,10 @@ _NO_LIMIT = 1 << 62
 class GenerationEngine:
     def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8, num_blocks: int = 256,
                  page_size: int = 16, prefill_chunk: Optional[int] = None):
-        from .llama import sample_tokens
-
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
         self._prefixes = {}
-
         self.model = model
         w = model.embed.weight
         self.cache = cache if cache is not None else PagedKVCache(model.cfg, num_blocks, page_size, device=w.device,
@@ -142,10 +140,7 @@ class GenerationEngine:
         blocks = -(-total // page) - whole // page  # shared pages are the prefix's, not the request's
         if blocks + (pfx.blocks if pfx is not None else 0) > self.cache.num_blocks:
             raise ValueError(f"request needs {blocks} cache blocks, the cache has {self.cache.num_blocks}")
-        gen = None
-        if temperature > 0:
-            gen = torch.Generator(device=self.model.embed.weight.device)
-            gen.manual_seed(0 if seed is None else int(seed))
+        gen = _seeded_generator(self.model.embed.weight.device, temperature, seed)
         rid = next(self._ids)
         req = _Request(rid, prompt, int(max_new_tokens), float(temperature), int(top_k), eos_token_id, gen, blocks,
                        seq_id=("engine", id(self), rid))
@@ -214,14 +209,64 @@ class GenerationEngine:
             self.waiting.appendleft(req)
             self.slots[slot] = None
 
-    def _extend_prefilling(self, events):
-        """Feed up to ``prefill_chunk`` prompt tokens of the prefilling requests, in arrival order
-        and in one ``extend`` call. A request whose prefix is not cached yet waits while the
-        prefix takes its turn. Returns the ids of the requests that finished their prompt."""
+    def _admit(self):
+        """Give free slots to waiting requests, in arrival order, as prefilling: a request that
+        does not fit waits (and keeps its place)."""
+        budget = self.cache.num_free_blocks - self._reserved()
+        while self.waiting and None in self.slots:
+            req = self.waiting[0]
+            pfx = req.prefix if req.prefix is not None and not req.prefix.reserved else None
+            need = req.blocks + (pfx.blocks if pfx is not None else 0)
+            if need > budget:
+                break
+            self.waiting.popleft()
+            budget -= need
+            if pfx is not None:
+                pfx.reserved = True
+            self.slots[self.slots.index(None)] = req
+            req.prefilling = True
+
+    def _feed(self, call, items, events):
+        """One prefill call over ``items`` ``(slot or None, request or prefix, tokens)``:
+        ``call(token lists, cache, seq_ids)`` gives one logits row per item. A request whose prompt
+        is now cached emits its first token and retires or stays; returns the ids of those that
+        stay. If the call fails it cached nothing (it is all or nothing): its requests go back to
+        the head of the queue in arrival order, so no slot decodes a sequence that was never
+        prefilled."""
+        try:
+            logits = call([t for _, _, t in items], self.cache, [o.seq_id for _, o, _ in items])
+        except Exception:
+            self._requeue([slot for slot, _, _ in items if slot is not None])
+            raise
+        done = set()
+        for i, (slot, obj, toks) in enumerate(items):
+            obj.fed += len(toks)
+            if slot is None or obj.fed < len(obj.feed):
+                continue
+            obj.prefilling = False
+            self._unhold_prefix(obj)
+            if self._emit(obj, logits[i], events):
+                self._retire(slot)
+            else:
+                done.add(obj.rid)
+        return done
+
+    def _prefill(self, events):
+        """The prompt work of one step. Requests with neither ``prefill_chunk`` nor a prefix take
+        one ``prefill`` call for their whole prompts and decode in this same step. The others are
+        fed up to ``prefill_chunk`` prompt tokens, in arrival order and in one ``extend`` call; a
+        request whose prefix is not cached yet waits while the prefix takes its turn. Returns the
+        ids of the requests that finished their prompt through ``extend``: they decode from the
+        next step on."""
+        if self.prefill_chunk is None:
+            plain = [(s, r, r.feed) for s, r in enumerate(self.slots)
+                     if r is not None and r.prefilling and r.prefix is None]
+            if plain:
+                self._feed(lambda toks, cache, ids: self.model.prefill(toks, None, cache, ids), plain, events)
         pre = sorted((s for s, r in enumerate(self.slots) if r is not None and r.prefilling),
                      key=lambda s: self.slots[s].rid)
         budget = self.prefill_chunk if self.prefill_chunk is not None else _NO_LIMIT
-        items, busy = [], set()  # (slot or None, request or prefix, tokens)
+        items, busy = [], set()
         for slot in pre:
             if budget <= 0:
                 break
@@ -241,67 +286,11 @@ class GenerationEngine:
             n = min(budget, len(req.feed) - req.fed)
             items.append((slot, req, req.feed[req.fed: req.fed + n]))
             budget -= n
-        joined = set()
-        if not items:
-            return joined
-        try:
-            logits = self.model.extend([t for _, _, t in items], self.cache, [o.seq_id for _, o, _ in items])
-        except Exception:
-            # extend cached nothing (it is all or nothing): its requests go back to the head of the
-            # queue in arrival order, so no slot decodes a sequence that was never prefilled
-            self._requeue([slot for slot, _, _ in items if slot is not None])
-            raise
-        for i, (slot, obj, toks) in enumerate(items):
-            obj.fed += len(toks)
-            if slot is None or obj.fed < len(obj.feed):
-                continue
-            obj.prefilling = False
-            self._unhold_prefix(obj)
-            if self._emit(obj, logits[i], events):
-                self._retire(slot)
-            else:
-                joined.add(obj.rid)  # decodes from the next step on
-        return joined
+        return self._feed(self.model.extend, items, events) if items else set()
 
-    def step(self) -> List[Tuple[int, int, bool]]:
-        """Admit, prefill, decode once, retire. Returns ``(request_id, token, finished)`` for every
-        token produced in this step, in production order."""
-        events: List[Tuple[int, int, bool]] = []
-        # admit in arrival order: a request that does not fit waits (and keeps its place)
-        admitted = []
-        budget = self.cache.num_free_blocks - self._reserved()
-        while self.waiting and None in self.slots:
-            req = self.waiting[0]
-            pfx = req.prefix if req.prefix is not None and not req.prefix.reserved else None
-            need = req.blocks + (pfx.blocks if pfx is not None else 0)
-            if need > budget:
-                break
-            self.waiting.popleft()
-            budget -= need
-            if pfx is not None:
-                pfx.reserved = True
-            slot = self.slots.index(None)
-            self.slots[slot] = req
-            if self.prefill_chunk is None and req.prefix is None:
-                admitted.append(slot)  # the plain path: one prefill, below
-            else:
-                req.prefilling = True
-        if admitted:
-            reqs = [self.slots[s] for s in admitted]
-            try:
-                logits = self.model.prefill([r.prompt for r in reqs], None, self.cache, [r.seq_id for r in reqs])
-            except Exception:
-                # prefill cached nothing (it is all or nothing): the requests go back to the head of
-                # the queue in arrival order, so no slot decodes a sequence that was never prefilled
-                for slot in reversed(admitted):
-                    self.waiting.appendleft(self.slots[slot])
-                    self.slots[slot] = None
-                raise
-            for i, slot in enumerate(admitted):
-                if self._emit(self.slots[slot], logits[i], events):
-                    self._retire(slot)
-        joined = self._extend_prefilling(events)
-        # requests still in their prompt, or that left it in this step, ride along as inactive slots
+    def _decode(self, joined, events):
+        """One decode step over the slots; requests still in their prompt, or that left it through
+        ``extend`` in this step (``joined``), ride along as inactive slots."""
         live = [r is not None and not r.prefilling and r.rid not in joined for r in self.slots]
         if any(live):
             seq_ids = [r.seq_id if on else None for r, on in zip(self.slots, live)]
@@ -310,4 +299,11 @@ class GenerationEngine:
             for slot, req in enumerate(self.slots):
                 if live[slot] and self._emit(req, logits[slot], events):
                     self._retire(slot)
+
+    def step(self) -> List[Tuple[int, int, bool]]:
+        """Admit, prefill, decode once, retire. Returns ``(request_id, token, finished)`` for every
+        token produced in this step, in production order."""
+        events: List[Tuple[int, int, bool]] = []
+        self._admit()
+        self._decode(self._prefill(events), events)
         return events

@@ -171,21 +171,24 @@ class Llama(nn.Module):
             self._cs[key] = t
         return t
 
-    def hidden_states(self, tokens, positions=None):
-        # the residual / norm chaining below is repeated in _run_layers (inference): keep them in step
-        B, S = tokens.shape
-        cs = self.rope_table(tokens.device)
-        residual = self.embed(tokens).view(B * S, -1)
+    def _run_layers(self, residual, attn):
+        """The layer stack on the embedded tokens ``[T, H]`` with ``attn(i, blk, h)`` as the
+        attention; returns the final-normed hidden states ``[T, H]``."""
         h = self.layers[0].attn_norm(residual) if len(self.layers) else residual
         for i, blk in enumerate(self.layers):
-            a = blk.attn(h, cs, B, S, positions)
+            a = attn(i, blk, h)
             h, residual = blk.mlp_norm(a, residual=residual)
             m = blk.mlp(h)
             nxt = self.layers[i + 1].attn_norm if i + 1 < len(self.layers) else self.norm
             h, residual = nxt(m, residual=residual)
         if not len(self.layers):
             h = self.norm(residual)
-        return h  # [T, H], final-normed
+        return h
+
+    def hidden_states(self, tokens, positions=None):
+        B, S = tokens.shape
+        cs = self.rope_table(tokens.device)
+        return self._run_layers(self.embed(tokens).view(B * S, -1), lambda i, blk, h: blk.attn(h, cs, B, S, positions))
 
     def logits(self, h):
         if self.lm_head is not None:
@@ -209,18 +212,41 @@ class Llama(nn.Module):
     # Generation over a paged KV cache (models/kv_cache.py). Under inference mode the fused-wgrad
     # linears and the fused embedding are plain ``F.linear`` / ``F.embedding`` (their autograd
     # paths are taken only when gradients are enabled), so the training modules are used as is.
-    def _run_layers(self, residual, attn):
-        """The layer stack of ``hidden_states`` with ``attn(i, blk, h)`` as the attention."""
-        h = self.layers[0].attn_norm(residual) if len(self.layers) else residual
-        for i, blk in enumerate(self.layers):
-            a = attn(i, blk, h)
-            h, residual = blk.mlp_norm(a, residual=residual)
-            m = blk.mlp(h)
-            nxt = self.layers[i + 1].attn_norm if i + 1 < len(self.layers) else self.norm
-            h, residual = nxt(m, residual=residual)
-        if not len(self.layers):
-            h = self.norm(residual)
-        return h
+    @staticmethod
+    def _allocate(cache, pairs):
+        """Cache slots for a batch of ``(seq_id, n_tokens)`` pairs, one list per pair. A ``None``
+        id is an inactive slot of a fixed-size batch: it takes nothing and gets slot -1. All or
+        nothing: a failed call (``KVCacheFull``) leaves the cache as it was."""
+        slots, done = [], []
+        try:
+            for s, n in pairs:
+                slots.append(cache.allocate(s, n) if s is not None else [-1] * n)
+                done.append((s, n))
+        except Exception:
+            for s, n in reversed(done):
+                if s is not None:
+                    cache.rollback(s, n)
+            raise
+        return slots
+
+    def _cached_forward(self, tokens, cache, slots, rope, attend, rows=None):
+        """The body of a forward over ``cache``: embed the flat ``tokens`` ``[T]``, run the layers
+        and return the logits of ``rows`` (indices into ``T``; ``None``: every row). Each layer
+        rotates its fused qkv with ``rope = (seq_len, positions)`` (``ops.apply_rope_``), appends
+        K/V at ``slots`` ``[T]`` and takes ``attend(i, blk, qkv)`` (which may read q in place from
+        the fused rows) as the projected attention output ``[T, H]``."""
+        cfg = self.cfg
+        D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
+        cs = self.rope_table(tokens.device)
+        seq_len, positions = rope
+
+        def attn(i, blk, h):
+            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, seq_len, Hq, Hk, D, positions)
+            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
+            return attend(i, blk, qkv)
+
+        h = self._run_layers(self.embed(tokens), attn)
+        return self.logits(h if rows is None else h[rows])
 
     @torch.inference_mode()
     def prefill(self, tokens, lengths, cache, seq_ids):
@@ -251,27 +277,13 @@ class Llama(nn.Module):
         keep = min(S, tokens.shape[1])
         padded[:, :keep] = tokens[:, :keep].to(dev)
         slots = torch.full((B, S), -1, dtype=torch.int32)
-        done = []
-        try:
-            for b, (sid, n) in enumerate(zip(seq_ids, lengths)):
-                slots[b, :n] = torch.tensor(cache.allocate(sid, n), dtype=torch.int32)
-                done.append(sid)
-        except Exception:
-            for sid in done:  # all or nothing
-                cache.free(sid)
-            raise
+        for b, s in enumerate(self._allocate(cache, zip(seq_ids, lengths))):
+            slots[b, :len(s)] = torch.tensor(s, dtype=torch.int32)
         slots = slots.reshape(-1).to(dev)
-        cs = self.rope_table(dev)
-        D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
-
-        def attn(i, blk, h):
-            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, S, Hq, Hk, D)
-            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
-            return blk.attn.causal_attention(qkv, B, S)
-
-        h = self._run_layers(self.embed(padded).view(B * S, -1), attn)
         last = torch.tensor([b * S + n - 1 for b, n in enumerate(lengths)], dtype=torch.long, device=dev)
-        return self.logits(h[last])  # the B x S x V logits are never formed
+        # the B x S x V logits are never formed
+        return self._cached_forward(padded.view(-1), cache, slots, (S, None),
+                                    lambda i, blk, qkv: blk.attn.causal_attention(qkv, B, S), last)
 
     @torch.inference_mode()
     def decode_step(self, tokens, cache, seq_ids):
@@ -287,30 +299,17 @@ class Llama(nn.Module):
         pos = [cache.length(s) if s is not None else 0 for s in seq_ids]
         if max(pos) >= cfg.max_seq_len:
             raise ValueError(f"sequence would exceed max_seq_len {cfg.max_seq_len}")
-        slots, done = [], []
-        try:
-            for s in seq_ids:
-                slots.append(cache.allocate(s, 1)[0] if s is not None else -1)
-                done.append(s)
-        except Exception:
-            for s in reversed(done):
-                if s is not None:  # give the one slot (and a block taken for it) back: all or nothing
-                    cache.rollback(s, 1)
-            raise
-        slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        slots = torch.tensor([s[0] for s in self._allocate(cache, [(s, 1) for s in seq_ids])], dtype=torch.int32,
+                             device=dev)
         positions = torch.tensor(pos, dtype=torch.int32, device=dev)
         block_table, context_lens = cache.block_table(seq_ids), cache.context_lens(seq_ids)
-        cs = self.rope_table(dev)
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
 
-        def attn(i, blk, h):
-            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, 1, Hq, Hk, D, positions)
-            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
-            # q is read in place from the fused row
+        def attend(i, blk, qkv):
             return blk.attn.o(ops.paged_attention_decode(qkv, cache.k[i], cache.v[i], block_table, context_lens,
                                                          Hq, Hk, D))
 
-        return self.logits(self._run_layers(self.embed(tokens), attn))
+        return self._cached_forward(tokens, cache, slots, (1, positions), attend)
 
     @torch.inference_mode()
     def extend(self, tokens, cache, seq_ids):
@@ -335,36 +334,23 @@ class Llama(nn.Module):
         start = [cache.length(s) for s in seq_ids]
         if max(p + len(r) for p, r in zip(start, rows)) > cfg.max_seq_len:
             raise ValueError(f"sequence would exceed max_seq_len {cfg.max_seq_len}")
-        slots, done = [], []
-        try:
-            for s, r in zip(seq_ids, rows):
-                slots.extend(cache.allocate(s, len(r)))
-                done.append((s, len(r)))
-        except Exception:
-            for s, n in reversed(done):  # all or nothing
-                cache.rollback(s, n)
-            raise
+        slots = self._allocate(cache, [(s, len(r)) for s, r in zip(seq_ids, rows)])
         flat = torch.tensor([t for r in rows for t in r], dtype=torch.long, device=dev)
-        slots = torch.tensor(slots, dtype=torch.int32, device=dev)
+        slots = torch.tensor([x for s in slots for x in s], dtype=torch.int32, device=dev)
         positions = torch.tensor([p + i for p, r in zip(start, rows) for i in range(len(r))], dtype=torch.int32,
                                  device=dev)
         cu = list(itertools.accumulate([len(r) for r in rows], initial=0))
         cu_q_lens = torch.tensor(cu, dtype=torch.int32, device=dev)
         max_q_len = max(len(r) for r in rows)
         block_table, context_lens = cache.block_table(seq_ids), cache.context_lens(seq_ids)
-        cs = self.rope_table(dev)
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
 
-        def attn(i, blk, h):
-            qkv = ops.apply_rope_(blk.attn.qkv(h), cs, 1, Hq, Hk, D, positions)
-            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
-            # q is read in place from the fused rows
+        def attend(i, blk, qkv):
             return blk.attn.o(ops.paged_attention_extend(qkv, cache.k[i], cache.v[i], block_table, context_lens,
                                                          cu_q_lens, max_q_len, Hq, Hk, D))
 
-        h = self._run_layers(self.embed(flat), attn)
         last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.long, device=dev)
-        return self.logits(h[last])
+        return self._cached_forward(flat, cache, slots, (1, positions), attend, last)
 
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
@@ -380,7 +366,6 @@ class Llama(nn.Module):
 
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
-
         prompts = [list(p) for p in prompts]
         if not prompts or max_new_tokens <= 0:
             return [[] for _ in prompts]
@@ -391,10 +376,7 @@ class Llama(nn.Module):
             page = 16
             blocks = sum(-(-(len(p) + max_new_tokens) // page) for p in prompts)
             cache = PagedKVCache(self.cfg, blocks, page, device=dev, dtype=self.embed.weight.dtype)
-        gen = None
-        if temperature > 0:
-            gen = torch.Generator(device=dev)
-            gen.manual_seed(0 if seed is None else int(seed))
+        gen = _seeded_generator(dev, temperature, seed)
         ids = [("generate", next(_SEQ_IDS)) for _ in prompts]
         out = [[] for _ in prompts]
         active = list(ids)
@@ -420,7 +402,6 @@ class Llama(nn.Module):
                 cache.free(sid)
         return out
 
-
     def _chunked_prefill(self, prompts, cache, ids, chunk):
         """``prefill`` through ``extend``: ``chunk`` tokens per unfinished prompt per call."""
         logits = [None] * len(prompts)
@@ -434,6 +415,16 @@ class Llama(nn.Module):
 
 
 _SEQ_IDS = itertools.count()
+
+
+def _seeded_generator(device, temperature, seed):
+    """The generator a request samples with: seeded (0 by default) on ``device``; ``None`` for
+    greedy decoding (``temperature == 0``)."""
+    if not temperature > 0:
+        return None
+    gen = torch.Generator(device=device)
+    gen.manual_seed(0 if seed is None else int(seed))
+    return gen
 
 
 def sample_tokens(logits, temperature: float = 0.0, top_k: int = 0, generator=None):

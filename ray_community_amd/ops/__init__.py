@@ -1104,6 +1104,36 @@ def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: i
     ref.kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D)
 
 
+def _check_paged_attention(letter, q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D):
+    """The argument checks the paged attention ops share; returns the number of sequences ``B``.
+    ``letter`` names q's rows: ``"B"`` (decode: one row per sequence, ``block_table`` checked
+    first) or ``"T"`` (extend: ``context_lens`` says how many sequences, and is checked first)."""
+    _check_paged_caches(k_cache, v_cache, Hk, D)
+    if q.dim() != 2 or q.shape[1] not in (Hq * D, (Hq + 2 * Hk) * D) or q.stride(1) != 1:
+        raise ValueError(f"q must be [{letter}, {Hq * D}] or the fused [{letter}, {(Hq + 2 * Hk) * D}] row with unit "
+                         f"inner stride, got {tuple(q.shape)}")
+    if q.dtype != k_cache.dtype or q.device != k_cache.device:
+        raise ValueError("q and the caches must share dtype and device")
+    B = q.shape[0] if letter == "B" else None
+    for name in ("block_table", "context_lens") if letter == "B" else ("context_lens", "block_table"):
+        t = block_table if name == "block_table" else context_lens
+        if name == "block_table" and (t.dim() != 2 or t.shape[1] < 1):
+            raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(t.shape)}")
+        if name == "context_lens" and t.dim() != 1:
+            raise ValueError(f"context_lens must be 1-D, got shape {tuple(t.shape)}")
+        B = t.shape[0] if B is None else B
+        _check_index(name, t, B, q.device)
+    return B
+
+
+def _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D, *more) -> bool:
+    """Whether the gfx950 paged attention kernels take this call (otherwise: the reference)."""
+    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
+    return (q.is_cuda and q.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
+            and q.stride(0) % 8 == 0 and q.data_ptr() % 16 == 0 and B <= 65535 and Hk <= 65535 and num_blocks > 0
+            and all(more))
+
+
 def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens, Hq: int, Hk: int, D: int,
                            scale=None, num_splits=None):
     """Single-token attention of ``B`` sequences over their paged KV caches. Returns ``[B, Hq*D]``.
@@ -1114,26 +1144,13 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
     never influence the result (whatever bytes their slots hold), and a length of 0 gives a zero
     row. ``num_splits`` (default: ``rca_attn_decode_num_splits`` on ``max_blocks * page_size``)
     splits each sequence's pages over that many workgroups, merged in a fixed order."""
-    _check_paged_caches(k_cache, v_cache, Hk, D)
-    if q_or_qkv.dim() != 2 or q_or_qkv.shape[1] not in (Hq * D, (Hq + 2 * Hk) * D) or q_or_qkv.stride(1) != 1:
-        raise ValueError(f"q must be [B, {Hq * D}] or the fused [B, {(Hq + 2 * Hk) * D}] row with unit inner "
-                         f"stride, got {tuple(q_or_qkv.shape)}")
-    if q_or_qkv.dtype != k_cache.dtype or q_or_qkv.device != k_cache.device:
-        raise ValueError("q and the caches must share dtype and device")
-    B = q_or_qkv.shape[0]
-    if block_table.dim() != 2 or block_table.shape[1] < 1:
-        raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(block_table.shape)}")
-    _check_index("block_table", block_table, B, q_or_qkv.device)
-    if context_lens.dim() != 1:
-        raise ValueError(f"context_lens must be 1-D, got shape {tuple(context_lens.shape)}")
-    _check_index("context_lens", context_lens, B, q_or_qkv.device)
+    q = q_or_qkv
+    B = _check_paged_attention("B", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("num_splits must be >= 1")
     scale = float(D ** -0.5 if scale is None else scale)
     num_blocks, page = k_cache.shape[0], k_cache.shape[1]
-    q = q_or_qkv
-    if not (q.is_cuda and q.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
-            and q.stride(0) % 8 == 0 and q.data_ptr() % 16 == 0 and B <= 65535 and Hk <= 65535 and num_blocks > 0):
+    if not _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D):
         return ref.paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale)
     out = torch.empty(B, Hq * D, device=q.device, dtype=q.dtype)
     if B == 0:
@@ -1171,32 +1188,18 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     max_blocks]``). Tokens past a context length never influence the result. ``max_q_len`` is an
     upper bound on the chunk lengths known on the host (it sizes the launch: no device
     synchronisation here; longer chunks are cut to it); rows no sequence owns are undefined."""
-    _check_paged_caches(k_cache, v_cache, Hk, D)
-    if q_or_qkv.dim() != 2 or q_or_qkv.shape[1] not in (Hq * D, (Hq + 2 * Hk) * D) or q_or_qkv.stride(1) != 1:
-        raise ValueError(f"q must be [T, {Hq * D}] or the fused [T, {(Hq + 2 * Hk) * D}] row with unit inner "
-                         f"stride, got {tuple(q_or_qkv.shape)}")
-    if q_or_qkv.dtype != k_cache.dtype or q_or_qkv.device != k_cache.device:
-        raise ValueError("q and the caches must share dtype and device")
-    T = q_or_qkv.shape[0]
-    if context_lens.dim() != 1:
-        raise ValueError(f"context_lens must be 1-D, got shape {tuple(context_lens.shape)}")
-    B = context_lens.shape[0]
-    _check_index("context_lens", context_lens, B, q_or_qkv.device)
-    if block_table.dim() != 2 or block_table.shape[1] < 1:
-        raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(block_table.shape)}")
-    _check_index("block_table", block_table, B, q_or_qkv.device)
+    q = q_or_qkv
+    B = _check_paged_attention("T", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D)
+    T = q.shape[0]
     if cu_q_lens.dim() != 1:
         raise ValueError(f"cu_q_lens must be 1-D, got shape {tuple(cu_q_lens.shape)}")
-    _check_index("cu_q_lens", cu_q_lens, B + 1, q_or_qkv.device)
+    _check_index("cu_q_lens", cu_q_lens, B + 1, q.device)
     max_q_len = int(max_q_len)
     if max_q_len < 0 or max_q_len > T:
         raise ValueError(f"max_q_len must be between 0 and T = {T}, got {max_q_len}")
     scale = float(D ** -0.5 if scale is None else scale)
     num_blocks, page = k_cache.shape[0], k_cache.shape[1]
-    q = q_or_qkv
-    if not (q.is_cuda and q.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
-            and q.stride(0) % 8 == 0 and q.data_ptr() % 16 == 0 and B <= 65535 and Hk <= 65535 and num_blocks > 0
-            and num_blocks * page < 2 ** 31 and scale > 0):
+    if not _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D, num_blocks * page < 2 ** 31, scale > 0):
         return ref.paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, cu_q_lens, Hq, Hk, D,
                                               scale)
     out = torch.empty(T, Hq * D, device=q.device, dtype=q.dtype)

@@ -244,6 +244,16 @@ def test_cache_rollback_is_exact():
     assert cache.num_free_blocks == 1 and "new" not in cache._lens and "new" not in cache._blocks
 
 
+def test_failed_prefill_leaves_the_cache_as_it_was():
+    m = _model()
+    cache = PagedKVCache(m.cfg, 4, 16, dtype=torch.float32)
+    with pytest.raises(KVCacheFull):  # 3 blocks for the first prompt, then 2 more for the second
+        m.prefill([_prompt(40, 71), _prompt(20, 72)], None, cache, ["a", "b"])
+    assert cache.num_free_blocks == cache.num_blocks == 4
+    assert "a" not in cache._lens and "a" not in cache._blocks
+    assert cache.allocate("x", 64) == list(range(64))  # the free list is in its original order
+
+
 def test_engine_cancel_frees_slot_and_blocks():
     m = _model()
     eng = GenerationEngine(m, max_slots=1, num_blocks=8)
