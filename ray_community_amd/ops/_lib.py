@@ -57,7 +57,6 @@ _SIGS = {
     "rca_standardize": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_float, c_void_p]),
     "rca_batched_copy": (c_int, [c_void_p, c_int, c_void_p, c_ll, c_void_p]),
     "rca_attn_fwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_ll] * 4 + [c_float, c_int, c_void_p]),
-    "rca_attn_bwd": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_ll] * 8 + [c_float, c_int, c_void_p]),
     "rca_attn_bwd2": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_ll] * 8 + [c_float, c_int, c_void_p, c_ll, c_void_p]),
     "rca_attn_bwd_ws_bytes": (c_ll, [c_int] * 6),
     "rca_attn_set_bwd_mode": (c_int, [c_int]),

@@ -25,24 +25,11 @@
 // Reference behaviour: torch SDPA / flash-attention semantics as used by the reference's Train
 // examples (python/ray/train/examples, release/train_tests) — the reference itself has no kernel.
 #include "attention_common.h"
+#include "attention_host.h"
 
 #include <cstdlib>
-
-// dK/dV lives in attention_dkdv.hip (its own register-form flags)
-void rca_attn_launch_dkdv(int D, bool causal, const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* dout,
-                          const float* lse, const float* delta, bf16_t* dk, bf16_t* dv, int B, int S, int Hq, int Hk,
-                          long sq, long sk, long sv, long sdo, long sdk, long sdv, float scale2, float scale,
-                          hipStream_t st, bf16_t* dSw, long tiles_bh);
-// recompute-free dQ (attention_dq.hip)
-long rca_attn_ds_ws_bytes(int B, int S, int Hq, int D, bool causal);
-void rca_attn_launch_delta(const bf16_t* o, const bf16_t* dout, float* delta, int B, int S, int Hq, long so, long sdo,
-                           hipStream_t st);
-void rca_attn_launch_dq_ds(bool causal, const bf16_t* k, const bf16_t* dsw, bf16_t* dq, int B, int S, int Hq, int Hk,
-                           long sk, long sdq, float scale, hipStream_t st);
-// 64-query-rows-per-wave forward (attention_fwd_wide.hip); false = not selected for this shape
-bool rca_attn_launch_fwd_wide(bool causal, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse,
-                              int B, int S, int Hq, int Hk, long sq, long sk, long sv, long so, float scale2,
-                              hipStream_t st);
+#include <cstring>
+#include <utility>
 
 namespace {
 
@@ -412,60 +399,116 @@ __global__ __launch_bounds__(kThreads, 2) void attn_bwd_dq_kernel(
   }
 }
 
-bool attn_dma() {
-  static const bool on = [] {
-    const char* e = getenv("RCA_ATTN_DMA");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
+// ---------------------------------------------------------------------------------------------
+// Kernel selection: every A/B switch of the five attention files. Read from the environment once,
+// when the library loads; the rca_attn_set_* entry points change a field at run time (same-process
+// A/B and the equivalence tests) and return the previous value.
+struct Policy {
+  // RCA_ATTN_DMA=0: the 4-wave forward stages K/V through registers instead of by LDS-DMA
+  bool dma;
+  // RCA_ATTN_FWD_NW, rca_attn_set_fwd_nw: waves per forward workgroup, 8 (default: one 256-row
+  // workgroup per CU, K/V staged once for all 8 waves) or 4 (two 128-row workgroups per CU).
+  // Interleaved A/B at the 8B shape, 3 rounds: 0.273 / 0.273 / 0.273 ms vs 0.279 / 0.278 / 0.279;
+  // bitwise-equal outputs (tests/test_attention_gpu.py).
+  int fwd_nw;
+  // RCA_ATTN_FWD, rca_attn_set_fwd_mode: forward kernel for D = 128. 0 = 32 rows per wave (this
+  // file), 1 = 64 rows per wave ("wide", attention_fwd_wide.hip), 2 = the hand-scheduled 64-row
+  // kernel ("hs", attention_fwd_hs.hip); 1 and 2 need S % 256 == 0. Also measured and dropped: the
+  // 32-row kernel with s_setprio(1) around its MFMA clusters, 0.296 vs 0.288 ms
+  // (profiles/attn_fwd_wide_ab_r4.log).
+  int fwd_mode;
+  // RCA_ATTN_HS_THR: deferred-rescale threshold of the hand-scheduled forward (log2 units; tests)
+  float hs_thr;
+  // RCA_ATTN_BWD, rca_attn_set_bwd_mode: 1 (default) = recompute-free dQ from the dS tiles the
+  // dK/dV kernel writes (needs the workspace of rca_attn_bwd_ws_bytes; D = 128), 0 = the dQ kernel
+  // that recomputes S, P and dP.
+  int bwd_mode;
+  // RCA_ATTN_DKDV=base, rca_attn_set_dkdv_hs: dK/dV kernel of the recompute path. 0 = compiler-
+  // scheduled, 1 (default for D = 128) = hand-scheduled with LDS-DMA staging, 2 = hand-scheduled
+  // with register staging (setter only: bisect / A/B).
+  int dkdv;
+  // RCA_ATTN_DKDV_NH=1: the unpipelined 32-row-slice form of the compiler-scheduled dK/dV kernel
+  int dkdv_nh;
+  // RCA_ATTN_HS_NOPS, rca_attn_set_hs_nops: wait states ahead of each asm MFMA of the dS-storing
+  // dK/dV kernel, as the s_nop operand: 1 (2 wait states; the default) or 3. 2 is the documented
+  // requirement for the hazard these nops cover -- a VALU write (or v_accvgpr_write) of a register
+  // that the next MFMA reads as its A/B operand: cdna_hip_programming.md §3 'A/B operands may be
+  // AGPRs' and §5.7 item 2, which is also the count LLVM's hazard recognizer inserts for this pair
+  // outside asm. Same-process A/B: bwd 1.025-1.050 vs 1.058-1.081 ms, 8B step 345.7 vs 349.0 ms
+  // median; gradients bitwise equal between the two counts on causal and full masks, MHA and GQA
+  // group sizes 1-8 (tests/test_attention_gpu.py::test_ds_kernel_wait_state_variants_agree_bitwise).
+  int hs_nops;
+  // RCA_ATTN_DQ_QW, rca_attn_set_dq_qw: query blocks per wave of the dQ-from-dS kernel, 2 (default:
+  // the K tile staged once per 256 query rows) or 1. Interleaved A/B, attention backward at the 8B
+  // shape: 1.019 / 1.054 / 1.064 ms vs 1.036 / 1.051 / 1.073; the 8B step 346.25 vs 348.08 ms
+  // median (scripts/step_ab.py, 3 rounds); dQ bitwise equal to the 1-block form.
+  int dq_qw;
+};
+
+Policy policy_from_env() {
+  auto is = [](const char* name, int v) {
+    const char* e = getenv(name);
+    return e && atoi(e) == v;
+  };
+  const char* fwd = getenv("RCA_ATTN_FWD");
+  const char* thr = getenv("RCA_ATTN_HS_THR");
+  const char* dkdv = getenv("RCA_ATTN_DKDV");
+  Policy p;
+  p.dma = !is("RCA_ATTN_DMA", 0);
+  p.fwd_nw = is("RCA_ATTN_FWD_NW", 4) ? 4 : 8;
+  p.fwd_mode = !fwd ? 0 : fwd[0] == 'w' ? 1 : fwd[0] == 'h' ? 2 : 0;
+  p.hs_thr = thr ? (float)atof(thr) : 8.f;
+  p.bwd_mode = is("RCA_ATTN_BWD", 0) ? 0 : 1;
+  p.dkdv = dkdv && strcmp(dkdv, "base") == 0 ? 0 : 1;
+  p.dkdv_nh = is("RCA_ATTN_DKDV_NH", 1) ? 1 : 2;
+  p.hs_nops = is("RCA_ATTN_HS_NOPS", 3) ? 3 : 1;
+  p.dq_qw = is("RCA_ATTN_DQ_QW", 1) ? 1 : 2;
+  return p;
 }
 
-// waves per forward workgroup: 8 (default: one 256-row workgroup per CU, K/V staged once for all
-// 8 waves) or 4 (two 128-row workgroups per CU) (RCA_ATTN_FWD_NW; run-time switch
-// rca_attn_set_fwd_nw). Interleaved A/B at the 8B shape, 3 rounds: 0.273 / 0.273 / 0.273 ms vs
-// 0.279 / 0.278 / 0.279; bitwise-equal outputs (tests/test_attention_gpu.py).
-int g_fwd_nw = [] {
-  const char* e = getenv("RCA_ATTN_FWD_NW");
-  return e && atoi(e) == 4 ? 4 : 8;
-}();
+Policy g_policy = policy_from_env();
 
-template <int D, bool C>
-void launch_fwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, int B, int S, int Hq,
-                int Hk, long sq, long sk, long sv, long so, float scale2, hipStream_t st) {
-  if (D == 128 && rca_attn_launch_fwd_wide(C, q, k, v, o, lse, B, S, Hq, Hk, sq, sk, sv, so, scale2, st)) return;
-  if (g_fwd_nw == 8 && S % 256 == 0 && attn_dma()) {
-    hipLaunchKernelGGL((attn_fwd_kernel<D, C, true, 8>), dim3(B * Hq * (S / 256)), dim3(512), 0, st, q, k, v, o, lse, B,
-                       S, Hq, Hk, sq, sk, sv, so, scale2);
-    return;
-  }
-  const int grid = B * Hq * (S / 128);
-  if (attn_dma())
-    hipLaunchKernelGGL((attn_fwd_kernel<D, C, true>), dim3(grid), dim3(kThreads), 0, st, q, k, v, o, lse, B, S, Hq, Hk,
-                       sq, sk, sv, so, scale2);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<D, C, false>), dim3(grid), dim3(kThreads), 0, st, q, k, v, o, lse, B, S, Hq,
-                       Hk, sq, sk, sv, so, scale2);
+// Which forward kernel runs, top to bottom.
+void launch_fwd(const AttnFwd& a) {
+  const Policy& p = g_policy;
+  const bool s256 = a.S % 256 == 0;
+  if (a.D == 128 && p.fwd_mode == 2 && s256) return rca_attn_launch_fwd_hs(a, p.hs_thr);
+  if (a.D == 128 && p.fwd_mode == 1 && s256) return rca_attn_launch_fwd_wide(a);
+  with_dim(a.D, [&](auto d) {
+    with_bool(a.causal, [&](auto c) {
+      constexpr int D = decltype(d)::value;
+      constexpr bool C = decltype(c)::value;
+      auto run = [&](auto kern, int nw) {  // a workgroup of nw waves covers 32 nw query rows
+        hipLaunchKernelGGL(kern, dim3(a.B * a.Hq * (a.S / (32 * nw))), dim3(64 * nw), 0, a.st, a.q, a.k, a.v, a.o,
+                           a.lse, a.B, a.S, a.Hq, a.Hk, a.sq, a.sk, a.sv, a.so, a.scale2);
+      };
+      if (p.fwd_nw == 8 && s256 && p.dma) run(attn_fwd_kernel<D, C, true, 8>, 8);
+      else if (p.dma) run(attn_fwd_kernel<D, C, true, 4>, 4);
+      else run(attn_fwd_kernel<D, C, false, 4>, 4);
+    });
+  });
 }
 
-template <int D, bool C>
-void launch_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout,
-                const float* lse, float* delta, bf16_t* dq, bf16_t* dk, bf16_t* dv, int B, int S, int Hq, int Hk,
-                long sq, long sk, long sv, long so, long sdo, long sdq, long sdk, long sdv, float scale2, float scale,
-                hipStream_t st, bf16_t* ws) {
-  if (ws != nullptr) {
+// Which backward kernels run, top to bottom.
+void launch_bwd(const AttnBwd& a) {
+  const Policy& p = g_policy;
+  if (a.ws != nullptr) {
     // recompute-free: delta, then dK/dV (+ the dS tiles), then dQ = dS . K
-    const long nb = S / 32, tiles = C ? nb * (nb + 1) / 2 : nb * nb;
-    rca_attn_launch_delta(o, dout, delta, B, S, Hq, so, sdo, st);
-    rca_attn_launch_dkdv(D, C, q, k, v, dout, lse, delta, dk, dv, B, S, Hq, Hk, sq, sk, sv, sdo, sdk, sdv, scale2,
-                         scale, st, ws, tiles);
-    rca_attn_launch_dq_ds(C, k, ws, dq, B, S, Hq, Hk, sk, sdq, scale, st);
+    rca_attn_launch_delta(a);
+    rca_attn_launch_dkdv_ds(a, p.hs_nops == 1 ? 1 : 3);
+    rca_attn_launch_dq_ds(a, p.dq_qw == 2 && a.S % 256 == 0 ? 2 : 1);
     return;
   }
   // dQ first: it also produces delta = rowsum(dO * O), which dK/dV reads
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, C>), dim3(B * Hq * (S / 128)), dim3(kThreads), 0, st, q, k, v, o, dout, lse,
-                     delta, dq, B, S, Hq, Hk, sq, sk, sv, so, sdo, sdq, scale2, scale);
-  rca_attn_launch_dkdv(D, C, q, k, v, dout, lse, delta, dk, dv, B, S, Hq, Hk, sq, sk, sv, sdo, sdk, sdv, scale2, scale,
-                       st, nullptr, 0);
+  with_dim(a.D, [&](auto d) {
+    with_bool(a.causal, [&](auto c) {
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<decltype(d)::value, decltype(c)::value>), dim3(a.B * a.Hq * (a.S / 128)),
+                         dim3(kThreads), 0, a.st, a.q, a.k, a.v, a.o, a.dout, a.lse, a.delta, a.dq, a.B, a.S, a.Hq,
+                         a.Hk, a.sq, a.sk, a.sv, a.so, a.sdo, a.sdq, a.scale2, a.scale);
+    });
+  });
+  if (a.D == 128 && p.dkdv != 0) rca_attn_launch_dkdv_hs(a, p.dkdv != 2);
+  else rca_attn_launch_dkdv(a, p.dkdv_nh);
 }
 
 bool shapes_ok(int B, int S, int Hq, int Hk, int D) {
@@ -473,49 +516,29 @@ bool shapes_ok(int B, int S, int Hq, int Hk, int D) {
          (long)B * S * Hq < (1L << 31);
 }
 
+constexpr float kLog2e = 1.4426950408889634f;
+
 }  // namespace
+
+RCA_API int rca_attn_set_fwd_nw(int nw) { return std::exchange(g_policy.fwd_nw, nw == 8 ? 8 : 4); }
+RCA_API int rca_attn_set_fwd_mode(int mode) { return std::exchange(g_policy.fwd_mode, mode); }
+RCA_API int rca_attn_set_bwd_mode(int mode) { return std::exchange(g_policy.bwd_mode, mode); }
+RCA_API int rca_attn_set_dkdv_hs(int on) { return std::exchange(g_policy.dkdv, on == 0 ? 0 : on == 2 ? 2 : 1); }
+RCA_API int rca_attn_set_hs_nops(int n) { return std::exchange(g_policy.hs_nops, n); }
+RCA_API int rca_attn_set_dq_qw(int q) { return std::exchange(g_policy.dq_qw, q == 2 ? 2 : 1); }
 
 RCA_API int rca_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
                          int Hk, int D, long long sq, long long sk, long long sv, long long so, float scale,
                          int causal, hipStream_t st) {
   if (!shapes_ok(B, S, Hq, Hk, D)) return 1;
-  const float scale2 = scale * 1.4426950408889634f;
-  auto Q = (const bf16_t*)q;
-  auto K = (const bf16_t*)k;
-  auto V = (const bf16_t*)v;
-  auto O = (bf16_t*)o;
-  if (D == 128) {
-    if (causal) launch_fwd<128, true>(Q, K, V, O, lse, B, S, Hq, Hk, sq, sk, sv, so, scale2, st);
-    else launch_fwd<128, false>(Q, K, V, O, lse, B, S, Hq, Hk, sq, sk, sv, so, scale2, st);
-  } else {
-    if (causal) launch_fwd<64, true>(Q, K, V, O, lse, B, S, Hq, Hk, sq, sk, sv, so, scale2, st);
-    else launch_fwd<64, false>(Q, K, V, O, lse, B, S, Hq, Hk, sq, sk, sv, so, scale2, st);
-  }
+  launch_fwd(AttnFwd{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, B, S, Hq, Hk, D, sq, sk, sv,
+                     so, scale, scale * kLog2e, causal != 0, st});
   return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-// Backward mode: 1 (default) = recompute-free dQ from the dS tiles the dK/dV kernel writes
-// (needs the workspace of rca_attn_bwd_ws_bytes; D = 128), 0 = the dQ kernel that recomputes S, P
-// and dP. RCA_ATTN_BWD=0 or rca_attn_set_bwd_mode(0) selects the latter (A/B, equivalence tests).
-static int g_bwd_mode = [] {
-  const char* e = getenv("RCA_ATTN_BWD");
-  return e && atoi(e) == 0 ? 0 : 1;
-}();
-RCA_API int rca_attn_set_bwd_mode(int mode) {
-  const int old = g_bwd_mode;
-  g_bwd_mode = mode;
-  return old;
-}
-
-RCA_API int rca_attn_set_fwd_nw(int nw) {
-  const int old = g_fwd_nw;
-  g_fwd_nw = nw == 8 ? 8 : 4;
-  return old;
 }
 
 // workspace bytes rca_attn_bwd2 wants for this shape (0: none, the recompute path runs)
 RCA_API long long rca_attn_bwd_ws_bytes(int B, int S, int Hq, int Hk, int D, int causal) {
-  if (g_bwd_mode != 1 || !shapes_ok(B, S, Hq, Hk, D)) return 0;
+  if (g_policy.bwd_mode != 1 || !shapes_ok(B, S, Hq, Hk, D)) return 0;
   return rca_attn_ds_ws_bytes(B, S, Hq, D, causal != 0);
 }
 
@@ -526,54 +549,10 @@ RCA_API int rca_attn_bwd2(const void* q, const void* k, const void* v, const voi
                           hipStream_t st) {
   if (!shapes_ok(B, S, Hq, Hk, D)) return 1;
   const long need = rca_attn_ds_ws_bytes(B, S, Hq, D, causal != 0);
-  bf16_t* w = (ws != nullptr && need > 0 && ws_bytes >= need && D == 128) ? (bf16_t*)ws : nullptr;
-  const float scale2 = scale * 1.4426950408889634f;
-  auto Q = (const bf16_t*)q;
-  auto K = (const bf16_t*)k;
-  auto V = (const bf16_t*)v;
-  auto O = (const bf16_t*)o;
-  auto G = (const bf16_t*)dout;
-  auto dQ = (bf16_t*)dq;
-  auto dK = (bf16_t*)dk;
-  auto dV = (bf16_t*)dv;
-#define RCA_BWD(DD, CC)                                                                                            \
-  launch_bwd<DD, CC>(Q, K, V, O, G, lse, delta, dQ, dK, dV, B, S, Hq, Hk, sq, sk, sv, so, sdo, sdq, sdk, sdv, scale2, \
-                     scale, st, DD == 128 ? w : nullptr)
-  if (D == 128) {
-    if (causal) RCA_BWD(128, true);
-    else RCA_BWD(128, false);
-  } else {
-    if (causal) RCA_BWD(64, true);
-    else RCA_BWD(64, false);
-  }
-#undef RCA_BWD
-  return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-RCA_API int rca_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                         const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hk,
-                         int D, long long sq, long long sk, long long sv, long long so, long long sdo, long long sdq,
-                         long long sdk, long long sdv, float scale, int causal, hipStream_t st) {
-  if (!shapes_ok(B, S, Hq, Hk, D)) return 1;
-  const float scale2 = scale * 1.4426950408889634f;
-  auto Q = (const bf16_t*)q;
-  auto K = (const bf16_t*)k;
-  auto V = (const bf16_t*)v;
-  auto O = (const bf16_t*)o;
-  auto G = (const bf16_t*)dout;
-  auto dQ = (bf16_t*)dq;
-  auto dK = (bf16_t*)dk;
-  auto dV = (bf16_t*)dv;
-#define RCA_BWD(DD, CC)                                                                                            \
-  launch_bwd<DD, CC>(Q, K, V, O, G, lse, delta, dQ, dK, dV, B, S, Hq, Hk, sq, sk, sv, so, sdo, sdq, sdk, sdv, scale2, \
-                     scale, st, nullptr)
-  if (D == 128) {
-    if (causal) RCA_BWD(128, true);
-    else RCA_BWD(128, false);
-  } else {
-    if (causal) RCA_BWD(64, true);
-    else RCA_BWD(64, false);
-  }
-#undef RCA_BWD
+  const bool use_ws = ws != nullptr && need > 0 && ws_bytes >= need && D == 128;
+  const long nb = S / 32, tiles = causal ? nb * (nb + 1) / 2 : nb * nb;
+  launch_bwd(AttnBwd{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, (const bf16_t*)dout, lse,
+                     delta, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, B, S, Hq, Hk, D, sq, sk, sv, so, sdo, sdq, sdk, sdv,
+                     scale, scale * kLog2e, causal != 0, st, use_ws ? (bf16_t*)ws : nullptr, tiles});
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

@@ -4,9 +4,7 @@
 // bursts (16 ds_read_b128 then 16 MFMAs) instead of read/wait/MFMA interleaving; measured 6 % less
 // backward time at the Llama-3-8B shape (scripts/gpu_attn_acc.sh).
 #include "attention_common.h"
-
-#include <cstdlib>
-#include <string>
+#include "attention_host.h"
 
 namespace {
 
@@ -660,93 +658,36 @@ RCA_HS_INST(false, true, true, 1)
 
 }  // namespace
 
-// The hand-scheduled dK/dV kernel is the default for D = 128 (RCA_ATTN_DKDV=base selects the
-// compiler-scheduled one); rca_attn_set_dkdv_hs switches at run time (same-process A/B and the
-// equivalence test), returning the previous setting.
-static bool g_dkdv_hs = [] {
-  const char* e = getenv("RCA_ATTN_DKDV");
-  return !(e && std::string(e) == "base");
-}();
-static bool g_dkdv_hs_stage = false;
-// wait states ahead of each asm MFMA of the dS-storing kernel: the s_nop operand, 1 (2 wait
-// states; the default) or 3. 2 is the documented requirement for the hazard these nops cover -- a
-// VALU write (or v_accvgpr_write) of a register that the next MFMA reads as its A/B operand:
-// cdna_hip_programming.md §3 'A/B operands may be AGPRs' and §5.7 item 2 ("a just-written "v"
-// operand or v_accvgpr_write -> MFMA operand (s_nop 1)", from cdna_asm_programming.md Table 38),
-// which is also the count LLVM's hazard recognizer inserts for this pair outside asm. Same-process
-// A/B: bwd 1.025-1.050 vs 1.058-1.081 ms, 8B step 345.7 vs 349.0 ms median; gradients bitwise
-// equal between the two counts on causal and full masks, MHA and GQA group sizes 1-8
-// (tests/test_attention_gpu.py::test_ds_kernel_wait_state_variants_agree_bitwise).
-static int g_hs_nops = [] {
-  const char* e = getenv("RCA_ATTN_HS_NOPS");
-  return e && atoi(e) == 3 ? 3 : 1;
-}();
-RCA_API int rca_attn_set_hs_nops(int n) {
-  const int old = g_hs_nops;
-  g_hs_nops = n;
-  return old;
-}
-// 0: compiler-scheduled kernel; 1: hand-scheduled (LDS-DMA staging); 2: hand-scheduled with
-// register staging
-RCA_API int rca_attn_set_dkdv_hs(int on) {
-  const int old = g_dkdv_hs ? (g_dkdv_hs_stage ? 2 : 1) : 0;
-  g_dkdv_hs = on != 0;
-  g_dkdv_hs_stage = on == 2;
-  return old;
+// the launch all three forms share; the hand-scheduled kernel takes (dS workspace, tiles) on top
+template <typename Kern, typename... Extra>
+static void launch(Kern kern, const AttnBwd& a, Extra... extra) {
+  hipLaunchKernelGGL(kern, dim3(a.B * a.Hk * (a.S / 128)), dim3(kThreads), 0, a.st, a.q, a.k, a.v, a.dout, a.lse,
+                     a.delta, a.dk, a.dv, a.B, a.S, a.Hq, a.Hk, a.sq, a.sk, a.sv, a.sdo, a.sdk, a.sdv, a.scale2, a.scale,
+                     extra...);
 }
 
-// dSw != nullptr: the hand-scheduled kernel also writes the dS tiles (D = 128 only; the caller checks)
-void rca_attn_launch_dkdv(int D, bool causal, const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* dout,
-                          const float* lse, const float* delta, bf16_t* dk, bf16_t* dv, int B, int S, int Hq, int Hk,
-                          long sq, long sk, long sv, long sdo, long sdk, long sdv, float scale2, float scale,
-                          hipStream_t st, bf16_t* dSw, long tiles_bh) {
-  // RCA_ATTN_DKDV_NH=1 selects the unpipelined 32-row-slice variant (A/B measurements);
-  // the hand-scheduled kernel for D = 128 unless RCA_ATTN_DKDV=base (g_dkdv_hs)
-  static const int nh = [] {
-    const char* e = getenv("RCA_ATTN_DKDV_NH");
-    return e && atoi(e) == 1 ? 1 : 2;
-  }();
-  const bool hs = g_dkdv_hs;
-  const dim3 grid(B * Hk * (S / 128)), block(kThreads);
-  if (dSw != nullptr) {
-#define RCA_DS(CC, NN)                                                                                           \
-  hipLaunchKernelGGL((attn_bwd_dkdv_hs_kernel<CC, true, true, NN>), grid, block, 0, st, q, k, v, dout, lse, delta, dk, \
-                     dv, B, S, Hq, Hk, sq, sk, sv, sdo, sdk, sdv, scale2, scale, dSw, tiles_bh)
-    if (g_hs_nops == 1) {
-      if (causal) RCA_DS(true, 1); else RCA_DS(false, 1);
-    } else {
-      if (causal) RCA_DS(true, 3); else RCA_DS(false, 3);
-    }
-#undef RCA_DS
-    return;
-  }
-  if (hs && D == 128) {
-#define RCA_HS(CC, MM)                                                                                         \
-  hipLaunchKernelGGL((attn_bwd_dkdv_hs_kernel<CC, MM, false, 3>), grid, block, 0, st, q, k, v, dout, lse, delta, dk, dv, \
-                     B, S, Hq, Hk, sq, sk, sv, sdo, sdk, sdv, scale2, scale, (bf16_t*)nullptr, 0L)
-    if (g_dkdv_hs_stage) {  // register staging (bisect / A/B)
-      if (causal) RCA_HS(true, false); else RCA_HS(false, false);
-    } else {
-      if (causal) RCA_HS(true, true); else RCA_HS(false, true);
-    }
-#undef RCA_HS
-    return;
-  }
-#define RCA_DKDV(DD, CC, NN)                                                                                           \
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, NN>), grid, block, 0, st, q, k, v, dout, lse, delta, dk, dv, B, S, \
-                     Hq, Hk, sq, sk, sv, sdo, sdk, sdv, scale2, scale)
-  if (D == 128) {
-    if (causal) {
-      if (nh == 1) RCA_DKDV(128, true, 1); else RCA_DKDV(128, true, 2);
-    } else {
-      if (nh == 1) RCA_DKDV(128, false, 1); else RCA_DKDV(128, false, 2);
-    }
-  } else {
-    if (causal) {
-      if (nh == 1) RCA_DKDV(64, true, 1); else RCA_DKDV(64, true, 2);
-    } else {
-      if (nh == 1) RCA_DKDV(64, false, 1); else RCA_DKDV(64, false, 2);
-    }
-  }
-#undef RCA_DKDV
+void rca_attn_launch_dkdv_ds(const AttnBwd& a, int nops) {
+  with_bool(a.causal, [&](auto c) {
+    with_bool(nops == 1, [&](auto one) {
+      launch(attn_bwd_dkdv_hs_kernel<decltype(c)::value, true, true, decltype(one)::value ? 1 : 3>, a, a.ws, a.tiles);
+    });
+  });
+}
+
+void rca_attn_launch_dkdv_hs(const AttnBwd& a, bool dma) {
+  with_bool(a.causal, [&](auto c) {
+    with_bool(dma, [&](auto m) {
+      launch(attn_bwd_dkdv_hs_kernel<decltype(c)::value, decltype(m)::value, false, 3>, a, (bf16_t*)nullptr, 0L);
+    });
+  });
+}
+
+void rca_attn_launch_dkdv(const AttnBwd& a, int nh) {
+  with_dim(a.D, [&](auto d) {
+    with_bool(a.causal, [&](auto c) {
+      with_bool(nh == 1, [&](auto one) {
+        launch(attn_bwd_dkdv_kernel<decltype(d)::value, decltype(c)::value, decltype(one)::value ? 1 : 2>, a);
+      });
+    });
+  });
 }

@@ -11,8 +11,7 @@
 // Also here: delta = rowsum(dO * O), which the dK/dV kernel reads (attention.hip fused it into
 // the dQ kernel, which now runs after dK/dV).
 #include "attention_common.h"
-
-#include <cstdlib>
+#include "attention_host.h"
 
 namespace {
 
@@ -198,39 +197,18 @@ long rca_attn_ds_ws_bytes(int B, int S, int Hq, int D, bool causal) {
   return ((long)B * Hq * tiles + 1) * 2048;
 }
 
-void rca_attn_launch_delta(const bf16_t* o, const bf16_t* dout, float* delta, int B, int S, int Hq, long so, long sdo,
-                           hipStream_t st) {
-  const long rows = (long)B * Hq * S;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, st, o, dout, delta, B, S, Hq,
-                     so, sdo);
+void rca_attn_launch_delta(const AttnBwd& a) {
+  const long rows = (long)a.B * a.Hq * a.S;
+  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, a.st, a.o, a.dout, a.delta,
+                     a.B, a.S, a.Hq, a.so, a.sdo);
 }
 
-// query blocks per wave of the dQ-from-dS kernel: 2 (default: the K tile staged once per 256 query
-// rows) or 1 (RCA_ATTN_DQ_QW; run-time switch rca_attn_set_dq_qw). Interleaved A/B, attention
-// backward at the 8B shape: 1.019 / 1.054 / 1.064 ms vs 1.036 / 1.051 / 1.073; with the 8-wave
-// forward the 8B step measured 346.25 vs 348.08 ms median (scripts/step_ab.py, 3 rounds); dQ bitwise
-// equal to the 1-block form.
-static int g_dq_qw = [] {
-  const char* e = getenv("RCA_ATTN_DQ_QW");
-  return e && atoi(e) == 1 ? 1 : 2;
-}();
-RCA_API int rca_attn_set_dq_qw(int q) {
-  const int old = g_dq_qw;
-  g_dq_qw = q == 2 ? 2 : 1;
-  return old;
-}
-
-void rca_attn_launch_dq_ds(bool causal, const bf16_t* k, const bf16_t* dsw, bf16_t* dq, int B, int S, int Hq, int Hk,
-                           long sk, long sdq, float scale, hipStream_t st) {
-  const long nb = S / 32, tiles = causal ? nb * (nb + 1) / 2 : nb * nb;
-  const int qw = (g_dq_qw == 2 && S % 256 == 0) ? 2 : 1;
-  const dim3 grid(B * Hq * (S / (128 * qw))), block(kThreads);
-#define RCA_DQ(CC, QQ) \
-  hipLaunchKernelGGL((attn_dq_ds_kernel<CC, QQ>), grid, block, 0, st, k, dsw, dq, B, S, Hq, Hk, sk, sdq, tiles, scale)
-  if (qw == 2) {
-    if (causal) RCA_DQ(true, 2); else RCA_DQ(false, 2);
-  } else {
-    if (causal) RCA_DQ(true, 1); else RCA_DQ(false, 1);
-  }
-#undef RCA_DQ
+void rca_attn_launch_dq_ds(const AttnBwd& a, int qw) {
+  with_bool(a.causal, [&](auto c) {
+    with_bool(qw == 2, [&](auto two) {
+      constexpr int QW = decltype(two)::value ? 2 : 1;
+      hipLaunchKernelGGL((attn_dq_ds_kernel<decltype(c)::value, QW>), dim3(a.B * a.Hq * (a.S / (128 * QW))),
+                         dim3(kThreads), 0, a.st, a.k, a.ws, a.dq, a.B, a.S, a.Hq, a.Hk, a.sk, a.sdq, a.tiles, a.scale);
+    });
+  });
 }

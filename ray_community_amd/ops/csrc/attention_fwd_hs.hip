@@ -23,8 +23,8 @@
 // kernel (0.271-0.292) -- opt-in. Waves whose causal rows end early keep joining the
 // barriers and issuing their DMA share (the pipeline drains one tile after a wave's last).
 #include "attention_common.h"
+#include "attention_host.h"
 
-#include <cstdlib>
 #include <utility>
 
 namespace {
@@ -363,21 +363,9 @@ template __global__ void attn_fwd_hs_kernel<false>(const bf16_t* __restrict__, c
 
 }  // namespace
 
-// S % 256 == 0 (the caller checks D == 128)
-bool rca_attn_launch_fwd_hs(bool causal, const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse,
-                            int B, int S, int Hq, int Hk, long sq, long sk, long sv, long so, float scale2,
-                            hipStream_t st) {
-  if (S % 256) return false;
-  static const float thr = [] {  // deferred-rescale threshold (log2 units); RCA_ATTN_HS_THR for tests
-    const char* e = getenv("RCA_ATTN_HS_THR");
-    return e ? (float)atof(e) : 8.f;
-  }();
-  const dim3 grid(B * Hq * (S / 256)), block(kThreads);
-  if (causal)
-    hipLaunchKernelGGL((attn_fwd_hs_kernel<true>), grid, block, 0, st, q, k, v, o, lse, B, S, Hq, Hk, sq, sk, sv, so,
-                       scale2, thr);
-  else
-    hipLaunchKernelGGL((attn_fwd_hs_kernel<false>), grid, block, 0, st, q, k, v, o, lse, B, S, Hq, Hk, sq, sk, sv, so,
-                       scale2, thr);
-  return true;
+void rca_attn_launch_fwd_hs(const AttnFwd& a, float thr) {
+  with_bool(a.causal, [&](auto c) {
+    hipLaunchKernelGGL((attn_fwd_hs_kernel<decltype(c)::value>), dim3(a.B * a.Hq * (a.S / 256)), dim3(kThreads), 0,
+                       a.st, a.q, a.k, a.v, a.o, a.lse, a.B, a.S, a.Hq, a.Hk, a.sq, a.sk, a.sv, a.so, a.scale2, thr);
+  });
 }

@@ -5,6 +5,8 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define RCA_API extern "C" __attribute__((visibility("default")))
 
 typedef unsigned short bf16_t;  // raw bf16 bits
@@ -12,6 +14,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int kWave = 64;
+
+// Host dispatch: a run-time bool -> a compile-time one. f receives std::true_type{} or
+// std::false_type{} (use ``decltype(flag)::value`` / ``flag.value`` as a template argument).
+template <typename F>
+auto with_bool(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
 
 __device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float(((unsigned)u) << 16); }
 

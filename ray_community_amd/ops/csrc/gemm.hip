@@ -120,46 +120,12 @@ __global__ __launch_bounds__(NTHR) void gemm_bf16_kernel(const bf16_t* __restric
   }
 }
 
-template <bool AK, bool BKM, bool ACC, int BK, int NS>
-int launch(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc, hipStream_t st) {
-  auto kern = gemm_bf16_kernel<AK, BKM, ACC, BK, NS>;
-  constexpr int smem = NS * 2 * 256 * BK * 2;
-  static bool attr = [&] {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  }();
-  if (!attr) return -3;
-  if (K % BK) return -1;
-  const int nwg = (M / BM) * (N / BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHR), smem, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K,
-                     lda, ldb, ldc);
-  return (int)hipGetLastError();
-}
-
-// Variants (RCA_GEMM_VARIANT, or rca_gemm_set_variant for same-process A/B):
-//   0: this file's 8-wave two-stage ring (round 2; fwd 1.15-1.24 PF, dgrad 0.97-1.04, wgrad
-//      0.82-0.98 on the 8B shapes, random operands, round-3 remeasure)
-//   2: gemm4.hip, one wave per SIMD with 128x128 wave tiles (default)
-template <bool AK, bool BKM, bool ACC>
-int launch_variant(int variant, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb,
-                   long ldc, hipStream_t st) {
-  (void)variant;
-  return launch<AK, BKM, ACC, 64, 2>(A, B, C, M, N, K, lda, ldb, ldc, st);
-}
-
-}  // namespace
-
-// Shape contract (checked here and by the Python wrapper): M % 256 == 0, N % 256 == 0,
-// K % 64 == 0; leading dimensions multiples of 8 elements and 16-B aligned base pointers.
-// a_kmaj / b_kmaj select the k-outer layouts; accumulate adds into C (bf16 read-modify-write).
-extern "C" int rca_gemm4_bf16_internal(const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                                       long long ldb, long long ldc, int a_kmaj, int b_kmaj, int accumulate,
-                                       hipStream_t st, int diag);
-
-static int g_gemm_variant = [] {
+int g_gemm_variant = [] {
   const char* e = getenv("RCA_GEMM_VARIANT");
   return e ? atoi(e) : 3;
 }();
-static int gemm_variant() { return g_gemm_variant; }
+
+}  // namespace
 
 // A/B switch for benchmarks (same process, interleaved rounds); returns the previous variant.
 RCA_API int rca_gemm_set_variant(int v) {
@@ -168,24 +134,50 @@ RCA_API int rca_gemm_set_variant(int v) {
   return old;
 }
 
+// Shape contract (checked here and by the Python wrapper): M % 256 == 0, N % 256 == 0,
+// K % 64 == 0; leading dimensions multiples of 8 elements and 16-B aligned base pointers.
+// a_kmaj / b_kmaj select the k-outer layouts; accumulate adds into C (bf16 read-modify-write).
+//
+// Variants (RCA_GEMM_VARIANT, or rca_gemm_set_variant for same-process A/B); all but 0 are gemm4.hip,
+// one wave per SIMD with 128x128 wave tiles:
+//   3 (default): 32-deep slices through a 4-stage ring; with row/row operands it runs as 7, which
+//      is faster on every measured shape (profiles/gemm_r4.md)
+//   0: this file's 8-wave two-stage ring (fwd 1.15-1.24 PF, dgrad 0.97-1.04, wgrad 0.82-0.98 on the
+//      8B shapes, random operands)
+//   2 (and any value not listed): the 4-wave two-stage loop
+//   5: the slice ring with partial waits
+//   6, 7, 71-78: buffer-addressed slice ring, full-line 64-deep tiles, and the schedule A/Bs of 7.
+//      Row/row operands only, K % 128 == 0, each operand < 4 GB: otherwise 3. 71-78 do not
+//      accumulate: with accumulate they run as 7.
+//   91, 92: timing diagnostics of 2 with deliberately WRONG results (no LDS-DMA inside the K loop /
+//      DMA never waited for), never accumulating. In general 90 + n is variant n (n = 0 as 2) without
+//      accumulate.
 RCA_API int rca_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, long long lda, long long ldb,
                           long long ldc, int a_kmaj, int b_kmaj, int accumulate, hipStream_t st) {
   if (M % BM || N % BN || K % 64 || M <= 0 || N <= 0 || K <= 0) return -1;
   if ((lda | ldb | ldc) & 7) return -2;
   if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) return -2;
-  int v = gemm_variant();
-  // k-contiguous (TN) operands: variant 7 (64-deep tiles, full-line DMA) is faster than 3 on
-  // every measured shape (profiles/gemm_r4.md); it falls back to 3 where its contract fails
-  if (v == 3 && !a_kmaj && !b_kmaj) v = 7;
-  if (v >= 90) return rca_gemm4_bf16_internal(A, B, C, M, N, K, lda, ldb, ldc, a_kmaj, b_kmaj, 0, st, v - 90);
-  if (v == 3 || v == 5 || v == 6 || v == 7 || (v >= 71 && v <= 78))
-    return rca_gemm4_bf16_internal(A, B, C, M, N, K, lda, ldb, ldc, a_kmaj, b_kmaj, accumulate, st, v);
-  if (v != 0) return rca_gemm4_bf16_internal(A, B, C, M, N, K, lda, ldb, ldc, a_kmaj, b_kmaj, accumulate, st, 0);
-#define RCA_G(a, b, c) return launch_variant<a, b, c>(v, A, B, C, M, N, K, lda, ldb, ldc, st)
-  if (!a_kmaj && !b_kmaj) { if (accumulate) RCA_G(false, false, true); RCA_G(false, false, false); }
-  if (!a_kmaj && b_kmaj) { if (accumulate) RCA_G(false, true, true); RCA_G(false, true, false); }
-  if (a_kmaj && b_kmaj) { if (accumulate) RCA_G(true, true, true); RCA_G(true, true, false); }
-  if (accumulate) RCA_G(true, false, true);
-  RCA_G(true, false, false);
-#undef RCA_G
+  const GemmArgs g{A, B, C, M, N, K, lda, ldb, ldc, st};
+  const bool rowrow = !a_kmaj && !b_kmaj;
+  int v = g_gemm_variant;
+  if (v == 3 && rowrow) v = 7;
+  const bool timing = v >= 90;
+  if (timing) {
+    v -= 90;
+    accumulate = 0;
+    if (v == 1 || v == 2) return rca_gemm4_bf16_internal(&g, a_kmaj, b_kmaj, 0, 90 + v);
+  }
+  if (v == 6 || v == 7 || (v >= 71 && v <= 78)) {
+    const bool fits = rowrow && K % 128 == 0 && (double)M * lda * 2 < 4294967296.0 &&
+                      (double)N * ldb * 2 < 4294967296.0;
+    if (!fits) v = 3;
+    else if (v >= 71 && accumulate) v = 7;
+  } else if (v == 0 && !timing) {
+    return dispatch_layout(a_kmaj, b_kmaj, accumulate, [&](auto ak, auto bk, auto acc) {
+      return launch_gemm<gemm_bf16_kernel<ak.value, bk.value, acc.value, 64, 2>>(2 * 2 * 256 * 64 * 2, NTHR, g);
+    });
+  } else if (v != 3 && v != 5) {
+    v = 2;
+  }
+  return rca_gemm4_bf16_internal(&g, a_kmaj, b_kmaj, accumulate, v);
 }

@@ -549,21 +549,6 @@ __global__ __launch_bounds__(NT4, 1) void gemm4b_kernel(const bf16_t* __restrict
   }
 }
 
-template <bool ACC>
-int launch4b(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc,
-             hipStream_t st) {
-  auto kern = gemm4b_kernel<ACC>;
-  constexpr int smem = 4 * SST;
-  static bool attr = [&] {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  }();
-  if (!attr) return -3;
-  const int nwg = (M / BM) * (N / BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT4), smem, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K,
-                     lda, ldb, ldc);
-  return (int)hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------------------------
 // Variant 7: full-cache-line LDS-DMA. A PMC pass on the o_proj forward product
 // (`profiles/gemm_r4.md`) showed variant 6's 32-deep slices costing twice hipBLASLt's L1->L2 read
@@ -884,117 +869,53 @@ __global__ __launch_bounds__(NT4, 1) void gemm4c_kernel(const bf16_t* __restrict
 
 template <bool ACC, int B1 = 24, int DS = 4, int W2 = 96, int RD = 2, int R1 = 1, int ORD = 1, int SPLIT = 1, int EPI = 0,
           int AUX = 0>
-int launch4c(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc,
-             hipStream_t st, EpiArgs ep = EpiArgs{}) {
+int launch4c(const GemmArgs& g, EpiArgs ep = EpiArgs{}) {
   static_assert(SPLIT || (B1 >= 16 * R1 && B1 + 15 * DS < W2 && W2 + 15 * RD < 128), "schedule positions");
-  auto kern = gemm4c_kernel<ACC, B1, DS, W2, RD, R1, ORD, SPLIT, EPI, AUX>;
-  constexpr int smem = EPI == 1 ? 4 * kEpiWaveLds : 4 * 256 * 128;
-  static bool attr = [&] {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  }();
-  if (!attr) return -3;
-  const int nwg = (M / BM) * (N / BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT4), smem, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K,
-                     lda, ldb, ldc, ep);
-  return (int)hipGetLastError();
+  return launch_gemm<gemm4c_kernel<ACC, B1, DS, W2, RD, R1, ORD, SPLIT, EPI, AUX>>(
+      EPI == 1 ? 4 * kEpiWaveLds : 4 * 256 * 128, NT4, g, ep);
 }
 
-template <bool AK, bool BKM, bool ACC, bool PW = false>
-int launch4s(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc,
-             hipStream_t st) {
-  auto kern = gemm4s_kernel<AK, BKM, ACC, PW>;
-  constexpr int smem = 4 * SST;
-  static bool attr = [&] {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  }();
-  if (!attr) return -3;
-  const int nwg = (M / BM) * (N / BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT4), smem, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K,
-                     lda, ldb, ldc);
-  return (int)hipGetLastError();
-}
-
-template <bool AK, bool BKM, bool ACC, int DIAG = 0>
-int launch4(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc, hipStream_t st) {
-  auto kern = gemm4_kernel<AK, BKM, ACC, DIAG>;
-  constexpr int smem = 2 * STG;
-  static bool attr = [&] {
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
-  }();
-  if (!attr) return -3;
-  const int nwg = (M / BM) * (N / BN);
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT4), smem, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, M, N, K,
-                     lda, ldb, ldc);
-  return (int)hipGetLastError();
+// the two-stage loop (variant 2); DIAG 1 / 2: its timing diagnostics (91 / 92), which exist for
+// three layouts (kmaj/row runs as kmaj/kmaj) and never accumulate
+template <int DIAG>
+int launch4_diag(const GemmArgs& g, bool a_kmaj, bool b_kmaj) {
+  if (!a_kmaj && !b_kmaj) return launch_gemm<gemm4_kernel<false, false, false, DIAG>>(2 * STG, NT4, g);
+  if (!a_kmaj) return launch_gemm<gemm4_kernel<false, true, false, DIAG>>(2 * STG, NT4, g);
+  return launch_gemm<gemm4_kernel<true, true, false, DIAG>>(2 * STG, NT4, g);
 }
 
 }  // namespace
 
-// Internal entry (dispatched from rca_gemm_bf16 in gemm.hip; shapes already checked there).
-extern "C" int rca_gemm4_bf16_internal(const void* A, const void* B, void* C, int M, int N, int K, long long lda,
-                                       long long ldb, long long ldc, int a_kmaj, int b_kmaj, int accumulate,
-                                       hipStream_t st, int diag) {
-  // timing diagnostics (WRONG results): 1 = no LDS-DMA inside the K loop, 2 = DMA issued but
-  // never waited for
-  if (diag == 1 || diag == 2) {
-#define RCA_G4D(D)                                                                         \
-  {                                                                                        \
-    if (!a_kmaj && !b_kmaj) return launch4<false, false, false, D>(A, B, C, M, N, K, lda, ldb, ldc, st); \
-    if (!a_kmaj && b_kmaj) return launch4<false, true, false, D>(A, B, C, M, N, K, lda, ldb, ldc, st);   \
-    return launch4<true, true, false, D>(A, B, C, M, N, K, lda, ldb, ldc, st);                           \
+// Launches exactly ``variant``; the routing and its table are in rca_gemm_bf16 (gemm.hip), which
+// has checked the shapes and, for 6 / 7 / 71-78, their row/row contract.
+extern "C" int rca_gemm4_bf16_internal(const GemmArgs* gp, int a_kmaj, int b_kmaj, int accumulate, int variant) {
+  const GemmArgs& g = *gp;
+  switch (variant) {
+    case 91: return launch4_diag<1>(g, a_kmaj, b_kmaj);
+    case 92: return launch4_diag<2>(g, a_kmaj, b_kmaj);
+    case 71: return launch4c<false, 20, 3, 88, 2, 1, 0, 0>(g);
+    case 72: return launch4c<false, 24, 4, 104, 1, 1, 0, 0>(g);
+    case 73: return launch4c<false, 32, 4, 100, 1, 1, 0, 0>(g);
+    case 74: return launch4c<false, 24, 4, 104, 1, 1, 1, 0>(g);
+    case 75: return launch4c<false, 36, 4, 100, 1, 2, 0, 0>(g);
+    case 76: return launch4c<false, 36, 4, 100, 1, 2, 1, 0>(g);
+    case 77: return launch4c<false, 24, 4, 96, 2, 1, 0, 1>(g);
+    case 78: return launch4c<false, 24, 4, 96, 2, 1, 1, 1>(g);
+    case 7: return with_bool(accumulate, [&](auto acc) { return launch4c<acc.value>(g); });
+    case 6:
+      return with_bool(accumulate, [&](auto acc) { return launch_gemm<gemm4b_kernel<acc.value>>(4 * SST, NT4, g); });
   }
-    if (diag == 1) RCA_G4D(1)
-    RCA_G4D(2)
-#undef RCA_G4D
-  }
-  // variants 6 / 7 (71-73: variant-7 schedule A/Bs): k-contiguous A and B, K % 128 == 0, every
-  // wave's buffer range < 4 GB; else 3
-  if (diag == 6 || diag == 7 || (diag >= 71 && diag <= 78)) {
-    if (!a_kmaj && !b_kmaj && K % 128 == 0 && (double)M * lda * 2 < 4294967296.0 &&
-        (double)N * ldb * 2 < 4294967296.0) {
-      if (diag >= 71 && accumulate) diag = 7;
-      if (diag == 71) return launch4c<false, 20, 3, 88, 2, 1, 0, 0>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 72) return launch4c<false, 24, 4, 104, 1, 1, 0, 0>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 73) return launch4c<false, 32, 4, 100, 1, 1, 0, 0>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 74) return launch4c<false, 24, 4, 104, 1, 1, 1, 0>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 75) return launch4c<false, 36, 4, 100, 1, 2, 0, 0>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 76) return launch4c<false, 36, 4, 100, 1, 2, 1, 0>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 77) return launch4c<false, 24, 4, 96, 2, 1, 0, 1>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 78) return launch4c<false, 24, 4, 96, 2, 1, 1, 1>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      if (diag == 7) {
-        if (accumulate) return launch4c<true>(A, B, C, M, N, K, lda, ldb, ldc, st);
-        return launch4c<false>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      }
-      if (accumulate) return launch4b<true>(A, B, C, M, N, K, lda, ldb, ldc, st);
-      return launch4b<false>(A, B, C, M, N, K, lda, ldb, ldc, st);
-    }
-    diag = 3;
-  }
-  if (diag == 5) {
-#define RCA_G4P(a, b, c) return launch4s<a, b, c, true>(A, B, C, M, N, K, lda, ldb, ldc, st)
-    if (!a_kmaj && !b_kmaj) { if (accumulate) RCA_G4P(false, false, true); RCA_G4P(false, false, false); }
-    if (!a_kmaj && b_kmaj) { if (accumulate) RCA_G4P(false, true, true); RCA_G4P(false, true, false); }
-    if (a_kmaj && b_kmaj) { if (accumulate) RCA_G4P(true, true, true); RCA_G4P(true, true, false); }
-    if (accumulate) RCA_G4P(true, false, true);
-    RCA_G4P(true, false, false);
-#undef RCA_G4P
-  }
-  if (diag == 3) {
-#define RCA_G4S(a, b, c) return launch4s<a, b, c>(A, B, C, M, N, K, lda, ldb, ldc, st)
-    if (!a_kmaj && !b_kmaj) { if (accumulate) RCA_G4S(false, false, true); RCA_G4S(false, false, false); }
-    if (!a_kmaj && b_kmaj) { if (accumulate) RCA_G4S(false, true, true); RCA_G4S(false, true, false); }
-    if (a_kmaj && b_kmaj) { if (accumulate) RCA_G4S(true, true, true); RCA_G4S(true, true, false); }
-    if (accumulate) RCA_G4S(true, false, true);
-    RCA_G4S(true, false, false);
-#undef RCA_G4S
-  }
-#define RCA_G4(a, b, c) return launch4<a, b, c>(A, B, C, M, N, K, lda, ldb, ldc, st)
-  if (!a_kmaj && !b_kmaj) { if (accumulate) RCA_G4(false, false, true); RCA_G4(false, false, false); }
-  if (!a_kmaj && b_kmaj) { if (accumulate) RCA_G4(false, true, true); RCA_G4(false, true, false); }
-  if (a_kmaj && b_kmaj) { if (accumulate) RCA_G4(true, true, true); RCA_G4(true, true, false); }
-  if (accumulate) RCA_G4(true, false, true);
-  RCA_G4(true, false, false);
-#undef RCA_G4
+  if (variant == 5)
+    return dispatch_layout(a_kmaj, b_kmaj, accumulate, [&](auto ak, auto bk, auto acc) {
+      return launch_gemm<gemm4s_kernel<ak.value, bk.value, acc.value, true>>(4 * SST, NT4, g);
+    });
+  if (variant == 3)
+    return dispatch_layout(a_kmaj, b_kmaj, accumulate, [&](auto ak, auto bk, auto acc) {
+      return launch_gemm<gemm4s_kernel<ak.value, bk.value, acc.value>>(4 * SST, NT4, g);
+    });
+  return dispatch_layout(a_kmaj, b_kmaj, accumulate, [&](auto ak, auto bk, auto acc) {
+    return launch_gemm<gemm4_kernel<ak.value, bk.value, acc.value>>(2 * STG, NT4, g);
+  });
 }
 
 // dgu, dgu_t = SwiGLU-backward(gu, dh) with dh = dy W_down computed in registers (variant 7's
@@ -1018,7 +939,7 @@ RCA_API int rca_gemm_affine_act(const void* x, const void* w, const float* shift
   ep.res = (const bf16_t*)res;
   ep.ldr = (long)ldr;
   ep.relu = relu;
-  return launch4c<false, 24, 4, 96, 2, 1, 1, 1, 2>(x, w, out, M, N, K, ldx, ldw, ldo, st, ep);
+  return launch4c<false, 24, 4, 96, 2, 1, 1, 1, 2>(GemmArgs{x, w, out, M, N, K, ldx, ldw, ldo, st}, ep);
 }
 
 RCA_API int rca_gemm_swiglu_bwd(const void* dy, const void* w_t, const void* gu, void* dgu, void* dgu_t, int T, int F,
@@ -1026,5 +947,5 @@ RCA_API int rca_gemm_swiglu_bwd(const void* dy, const void* w_t, const void* gu,
   if (T <= 0 || F <= 0 || H <= 0 || T % 256 || F % 256 || H % 128 || ld_dy % 8 || ld_w % 8) return -1;
   if ((double)T * ld_dy * 2 >= 4294967296.0 || (double)F * ld_w * 2 >= 4294967296.0) return -1;
   EpiArgs ep{(const bf16_t*)gu, (bf16_t*)dgu, (bf16_t*)dgu_t, 2L * F, 2L * F, (long)T, F};
-  return launch4c<false, 24, 4, 96, 2, 1, 1, 1, 1>(dy, w_t, nullptr, T, F, H, ld_dy, ld_w, 0, st, ep);
+  return launch4c<false, 24, 4, 96, 2, 1, 1, 1, 1>(GemmArgs{dy, w_t, nullptr, T, F, H, ld_dy, ld_w, 0, st}, ep);
 }

@@ -96,4 +96,45 @@ __device__ __forceinline__ void store4(bf16_t* __restrict__ C, long off, const f
          ((unsigned long long)f2bf(v2) << 32) | ((unsigned long long)f2bf(v3) << 48);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host side. The operands of one GEMM call as the entry points received them.
+struct GemmArgs {
+  const void *A, *B;
+  void* C;
+  int M, N, K;
+  long lda, ldb, ldc;
+  hipStream_t st;
+};
+
+// Launch Kern (A, B, C, M, N, K, lda, ldb, ldc, extra...) on the (M / BM) x (N / BN) tile grid. The
+// kernel's dynamic-LDS limit is raised once, at its first launch: -3 if that failed, else the
+// launch's HIP error (0 = ok).
+template <auto Kern, typename... Extra>
+int launch_gemm(int smem_bytes, int threads, const GemmArgs& g, Extra... extra) {
+  static const bool attr = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               smem_bytes) == hipSuccess;
+  if (!attr) return -3;
+  hipLaunchKernelGGL(Kern, dim3((g.M / BM) * (g.N / BN)), dim3(threads), smem_bytes, g.st, (const bf16_t*)g.A,
+                     (const bf16_t*)g.B, (bf16_t*)g.C, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, extra...);
+  return (int)hipGetLastError();
+}
+
+// f(a_kmaj, b_kmaj, accumulate) with the three flags as std::bool_constant values. The layouts are
+// spelled out in this order because hipcc emits the kernels in the order they are instantiated.
+template <typename F>
+int dispatch_layout(bool a_kmaj, bool b_kmaj, bool accumulate, F f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  auto layout = [&](auto ak, auto bk) { return with_bool(accumulate, [&](auto acc) { return f(ak, bk, acc); }); };
+  if (!a_kmaj && !b_kmaj) return layout(N{}, N{});
+  if (!a_kmaj) return layout(N{}, T{});
+  if (b_kmaj) return layout(T{}, T{});
+  return layout(T{}, N{});
+}
+
 }  // namespace rca_gemm
+
+// The one-wave-per-SIMD kernels (gemm4.hip). ``variant`` is already routed (rca_gemm_bf16, gemm.hip):
+// 2, 3, 5, or -- with their contract checked -- 6, 7, 71-78, or the timing diagnostics 91 / 92.
+extern "C" int rca_gemm4_bf16_internal(const rca_gemm::GemmArgs* g, int a_kmaj, int b_kmaj, int accumulate,
+                                       int variant);

@@ -333,3 +333,31 @@ def test_ds_kernel_wait_state_variants_agree_bitwise(causal, B, S, Hq, Hk):
             lib.rca_attn_set_hs_nops(prev)
     for a, b in zip(*outs):
         assert torch.equal(a, b)
+
+
+def test_policy_setters_return_previous_value_and_normalise():
+    """The six run-time switches: each setter returns the value it replaces (the documented default
+    on a fresh library) and stores its argument normalised as documented. Launches no kernel."""
+    import os
+
+    if any(name.startswith("RCA_ATTN_") for name in os.environ):
+        pytest.skip("an RCA_ATTN_* variable overrides the defaults")
+    lib = ops._lib.lib()
+    # setter -> (default, a non-default value, (argument, what the setter stores for it))
+    switches = {
+        "rca_attn_set_fwd_nw": (8, 4, (5, 4)),
+        "rca_attn_set_fwd_mode": (0, 2, (1, 1)),
+        "rca_attn_set_bwd_mode": (1, 0, (1, 1)),
+        "rca_attn_set_dkdv_hs": (1, 0, (2, 2)),
+        "rca_attn_set_hs_nops": (1, 3, (1, 1)),
+        "rca_attn_set_dq_qw": (2, 1, (3, 1)),
+    }
+    try:
+        for name, (default, other, (arg, stored)) in switches.items():
+            setter = getattr(lib, name)
+            assert setter(other) == default, name
+            assert setter(arg) == other, name
+            assert setter(default) == stored, name
+    finally:
+        for name, (default, _, _) in switches.items():
+            getattr(lib, name)(default)
