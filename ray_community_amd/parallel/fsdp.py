@@ -33,7 +33,6 @@ sitting in front of the backward's dgrad, which waits on its event only when it 
 from __future__ import annotations
 
 import contextlib
-import math
 import os
 from typing import Dict, List, Optional
 
@@ -44,7 +43,7 @@ import torch.nn as nn
 from .. import ops
 from .ddp import CommWaitTimer
 from .flat import ALIGN, FlatParameters, register_grad_ready
-from .optim import _use_split
+from .optim import AdamWBase
 
 
 class ShardedDataParallel(nn.Module):
@@ -232,20 +231,15 @@ class ShardedDataParallel(nn.Module):
         return self.module.load_state_dict(sd, strict=strict)
 
 
-class ShardedAdamW:
+class ShardedAdamW(AdamWBase):
     """AdamW over this rank's chunks of a ``ShardedDataParallel`` model (fp32 master + moments
     for owned elements only); same update rule as ``FlatAdamW`` / ``torch.optim.AdamW``."""
 
     def __init__(self, sdp: ShardedDataParallel, lr: float = 3e-4, betas=(0.9, 0.95), eps: float = 1e-8,
                  weight_decay: float = 0.1, max_grad_norm: Optional[float] = 1.0, lr_schedule=None,
                  master_format: str = "auto"):
-        self.sdp = sdp
+        self.sdp = self._shard = sdp
         flat = sdp.flat
-        self.lr, (self.b1, self.b2), self.eps, self.wd = lr, betas, eps, weight_decay
-        self.max_grad_norm = max_grad_norm
-        self.lr_schedule = lr_schedule
-        self.step_count = 0
-        self.master_weights = flat.dtype != torch.float32
         self.chunks = []  # (bucket index, flat start, flat end, local offset, weight decay)
         lo = 0
         for b in flat.buckets:
@@ -253,125 +247,44 @@ class ShardedAdamW:
             self.chunks.append((b.index, s, e, lo, weight_decay if b.start < flat.decay_end else 0.0))
             lo += e - s
         self.local_numel = lo
-        dev = flat.device
         # split master (optim.py): the owned chunks' bf16 weights hold the high halves, ``lo`` the
         # low 16 bits; needs 8-element-aligned chunks for the vector kernel
         aligned = all(s % 8 == 0 and o % 8 == 0 for _, s, _, o, _ in self.chunks)
         fmt = master_format if aligned or master_format == "fp32" else ("fp32" if master_format == "auto" else "unaligned")
         if fmt == "unaligned":
             raise ValueError("split master format needs 8-element-aligned shard chunks")
-        self.split_master = _use_split(fmt, self.master_weights, flat.data)
-        self.lo = torch.zeros(lo, dtype=torch.int16, device=dev) if self.split_master else None
-        self._master = None
-        if not self.split_master:
-            self._master = torch.empty(lo, dtype=torch.float32, device=dev)
-            for _, s, e, o, _ in self.chunks:
-                self._master[o: o + e - s].copy_(flat.data[s:e])
-        self.m = torch.zeros(lo, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(lo, dtype=torch.float32, device=dev)
-        self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._grad_scale = 1.0
+        super().__init__(self._owned_weights(), lr, betas, eps, weight_decay, max_grad_norm, lr_schedule,
+                         master_format=fmt)
 
-    @property
-    def param_groups(self):
-        return [{"lr": self.lr, "weight_decay": self.wd}]
-
-    def current_lr(self) -> float:
-        return self.lr_schedule(self.step_count) if self.lr_schedule else self.lr
-
-    def _hi_local(self) -> torch.Tensor:
+    def _owned_weights(self) -> torch.Tensor:
         flat = self.sdp.flat
         return torch.cat([flat.data[s:e] for _, s, e, _, _ in self.chunks]) if self.chunks else flat.data[:0]
-
-    @property
-    def master(self) -> torch.Tensor:
-        """fp32 master of the owned elements (split format: reconstructed, a fresh tensor)."""
-        if self.split_master:
-            return ops.reference.join_master(self._hi_local(), self.lo)
-        return self._master
 
     @torch.no_grad()
     def step(self, grad_scale: Optional[float] = None):
         sdp, flat = self.sdp, self.sdp.flat
-        grad_scale = sdp.grad_scale if grad_scale is None else grad_scale
-        self._grad_scale = grad_scale
-        self.step_count += 1
-        t = self.step_count
-        lr = self.current_lr()
-        bc1, bc2 = 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
         flat.finalize_fresh()
         sdp.invalidate_wt()
         g = flat.step_grad
-        clip = self.max_grad_norm if self.max_grad_norm and self.max_grad_norm > 0 else 0.0
-        if clip:
-            ops.grad_sumsq([g[s:e] for _, s, e, _, _ in self.chunks], out=self._sumsq)
-            if sdp.world > 1:
-                dist.all_reduce(self._sumsq, group=sdp.pg)
+        if self.clip:
+            self._global_sumsq([g[s:e] for _, s, e, _, _ in self.chunks], sdp.pg, sdp.world)
+        hp = self._begin_step(sdp.grad_scale if grad_scale is None else grad_scale)
         # update chunks in the order the next forward needs them, launching each bucket's gather
         order = {bi: k for k, bi in enumerate(sdp.gather_order())}
         for bi, s, e, o, wd in sorted(self.chunks, key=lambda c: order[c[0]]):
-            n = e - s
-            if n > 0:
-                if g.is_cuda:
-                    from ..ops._lib import check, lib, stream_ptr
-
-                    if g.dtype not in (torch.bfloat16, torch.float32):
-                        raise TypeError(f"unsupported grad dtype {g.dtype}")
-                    gdt = 0 if g.dtype == torch.bfloat16 else 1
-                    if self.split_master:
-                        check(lib().rca_adamw_split(flat.data.data_ptr() + s * 2, self.lo.data_ptr() + o * 2,
-                                                    g.data_ptr() + s * g.element_size(), gdt,
-                                                    self.m.data_ptr() + o * 4, self.v.data_ptr() + o * 4, n, lr,
-                                                    self.b1, self.b2, self.eps, wd, bc1, bc2, grad_scale,
-                                                    self._sumsq.data_ptr() if clip else 0, float(clip),
-                                                    stream_ptr(g.device)), "adamw_split")
-                        sdp.launch_all_gather(bi)
-                        continue
-                    p16 = flat.data.data_ptr() + s * flat.data.element_size() if self.master_weights else 0
-                    mp = self._master.data_ptr() + o * 4 if self.master_weights else 0
-                    if not self.master_weights:  # fp32 model: update the flat data in place
-                        mp = flat.data.data_ptr() + s * 4
-                    check(lib().rca_adamw(mp, p16, g.data_ptr() + s * g.element_size(), gdt,
-                                          self.m.data_ptr() + o * 4, self.v.data_ptr() + o * 4, n, lr, self.b1,
-                                          self.b2, self.eps, wd, bc1, bc2, grad_scale,
-                                          self._sumsq.data_ptr() if clip else 0, float(clip), stream_ptr(g.device)),
-                          "adamw")
-                else:
-                    coef = 1.0
-                    if clip:
-                        nrm = math.sqrt(float(self._sumsq)) * abs(grad_scale)
-                        coef = min(1.0, clip / (nrm + 1e-6))
-                    if self.split_master:
-                        master = ops.reference.join_master(flat.data[s:e], self.lo[o: o + n])
-                    else:
-                        master = self._master[o: o + n] if self.master_weights else flat.data[s:e]
-                    ops.reference.adamw_ref(master, g[s:e], self.m[o: o + n], self.v[o: o + n], lr, self.b1, self.b2,
-                                            self.eps, wd, t, grad_mul=grad_scale, clip=coef)
-                    if self.split_master:
-                        hi, lo_ = ops.reference.split_master(master)
-                        flat.data[s:e].copy_(hi)
-                        self.lo[o: o + n].copy_(lo_)
-                    elif self.master_weights:
-                        flat.data[s:e].copy_(master.to(flat.dtype))
+            self._update(flat.data[s:e], g[s:e], o, o + e - s, wd, hp)
             sdp.launch_all_gather(bi)
-
-    def grad_norm(self) -> float:
-        return math.sqrt(float(self._sumsq.item())) * abs(self._grad_scale)
 
     def zero_grad(self, set_to_none: bool = False):
         self.sdp.flat.zero_grad()
 
     def state_dict(self):
-        """This rank's shard of the optimizer state (save one file per rank)."""
-        return {"step": self.step_count, "m": self.m, "v": self.v, "master": self.master, "rank": self.sdp.rank,
-                "world": self.sdp.world, "lr": self.lr, "betas": (self.b1, self.b2), "eps": self.eps, "wd": self.wd}
+        sd = super().state_dict()
+        sd["master"] = self.master  # saved for fp32 models too
+        return sd
 
     def load_state_dict(self, sd):
-        if sd.get("world", self.sdp.world) != self.sdp.world:
-            raise ValueError("sharded optimizer state was saved with a different world size")
-        self.step_count = sd["step"]
-        self.m.copy_(sd["m"])
-        self.v.copy_(sd["v"])
+        self._load_moments(sd)
         self.sdp.invalidate_wt()
         flat = self.sdp.flat
         master = sd["master"].to(flat.device)

@@ -33,15 +33,14 @@ units + activations: see ``estimate_memory_gb`` (Llama-3-70B on 8 GPUs fits in 2
 from __future__ import annotations
 
 import contextlib
-import math
 from typing import Dict, List, Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from .. import ops
 from .flat import ALIGN, _round_up, default_no_decay, register_grad_ready
+from .optim import AdamWBase
 
 _FREE, _GATHERING, _READY = 0, 1, 2
 
@@ -486,7 +485,7 @@ class FullyShardedDataParallel(nn.Module):
             self._gather(self.root, wait=True)
 
 
-class FullyShardedAdamW:
+class FullyShardedAdamW(AdamWBase):
     """AdamW over the local shards of a ``FullyShardedDataParallel`` model: fp32 master weights
     and moments for this rank's chunks only; one fused HIP launch per contiguous weight-decay
     segment of the local buffer; global-norm clipping via a scalar all-reduce (no host sync).
@@ -494,18 +493,8 @@ class FullyShardedAdamW:
 
     def __init__(self, fsdp: FullyShardedDataParallel, lr: float = 3e-4, betas=(0.9, 0.95), eps: float = 1e-8,
                  weight_decay: float = 0.1, max_grad_norm: Optional[float] = 1.0, lr_schedule=None):
-        self.fsdp = fsdp
-        self.lr, (self.b1, self.b2), self.eps, self.wd = lr, betas, eps, weight_decay
-        self.max_grad_norm = max_grad_norm
-        self.lr_schedule = lr_schedule
-        self.step_count = 0
-        self.master_weights = fsdp.dtype != torch.float32
-        dev = fsdp.device
-        self.master = fsdp.local_data.float() if self.master_weights else fsdp.local_data
-        self.m = torch.zeros(fsdp.local_numel, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(fsdp.local_numel, dtype=torch.float32, device=dev)
-        self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._grad_scale = 1.0
+        self.fsdp = self._shard = fsdp
+        super().__init__(fsdp.local_data, lr, betas, eps, weight_decay, max_grad_norm, lr_schedule)
         # local segments (start, end, weight decay), adjacent equal-decay runs merged
         segs = []
         for u in fsdp.units:
@@ -520,79 +509,33 @@ class FullyShardedAdamW:
                         segs.append([ls, le, wd])
         self.segments = [tuple(x) for x in segs]
 
-    @property
-    def param_groups(self):
-        return [{"lr": self.lr, "weight_decay": self.wd}]
-
-    def current_lr(self) -> float:
-        return self.lr_schedule(self.step_count) if self.lr_schedule else self.lr
+    def _owned_weights(self) -> torch.Tensor:
+        return self.fsdp.local_data
 
     def sync_master(self):
         if self.master_weights:
-            self.master.copy_(self.fsdp.local_data.float())
+            self._master.copy_(self.fsdp.local_data.float())
 
     @torch.no_grad()
     def step(self, grad_scale: Optional[float] = None):
         f = self.fsdp
-        grad_scale = f.grad_scale if grad_scale is None else grad_scale
-        self._grad_scale = grad_scale
-        self.step_count += 1
-        t = self.step_count
-        lr = self.current_lr()
-        bc1, bc2 = 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
         g = f.local_grad
-        clip = self.max_grad_norm if self.max_grad_norm and self.max_grad_norm > 0 else 0.0
-        if clip:
-            ops.grad_sumsq([g], out=self._sumsq)
-            if f.world > 1:
-                dist.all_reduce(self._sumsq, group=f.pg)
-        if g.is_cuda:
-            from ..ops._lib import check, lib, stream_ptr
-
-            if g.dtype not in (torch.bfloat16, torch.float32):
-                raise TypeError(f"unsupported grad dtype {g.dtype}")
-            gdt = 0 if g.dtype == torch.bfloat16 else 1
-            st = stream_ptr(g.device)
-            for s, e, wd in self.segments:
-                p16 = f.local_data.data_ptr() + s * f.local_data.element_size() if self.master_weights else 0
-                check(lib().rca_adamw(self.master.data_ptr() + s * 4, p16, g.data_ptr() + s * g.element_size(), gdt,
-                                      self.m.data_ptr() + s * 4, self.v.data_ptr() + s * 4, e - s, lr, self.b1,
-                                      self.b2, self.eps, wd, bc1, bc2, grad_scale,
-                                      self._sumsq.data_ptr() if clip else 0, float(clip), st), "adamw")
-        else:
-            coef = 1.0
-            if clip:
-                nrm = math.sqrt(float(self._sumsq)) * abs(grad_scale)
-                coef = min(1.0, clip / (nrm + 1e-6))
-            for s, e, wd in self.segments:
-                ops.reference.adamw_ref(self.master[s:e], g[s:e], self.m[s:e], self.v[s:e], lr, self.b1, self.b2,
-                                        self.eps, wd, t, grad_mul=grad_scale, clip=coef)
-            if self.master_weights:
-                f.local_data.copy_(self.master.to(f.dtype))
+        if self.clip:
+            self._global_sumsq([g], f.pg, f.world)
+        hp = self._begin_step(f.grad_scale if grad_scale is None else grad_scale)
+        for s, e, wd in self.segments:
+            self._update(f.local_data[s:e], g[s:e], s, e, wd, hp)
         f.mark_stale()
-
-    def grad_norm(self) -> float:
-        return math.sqrt(float(self._sumsq.item())) * abs(self._grad_scale)
 
     def zero_grad(self, set_to_none: bool = False):
         self.fsdp.zero_grad()
 
-    def state_dict(self):
-        """This rank's shard of the optimizer state (save one file per rank)."""
-        return {"step": self.step_count, "m": self.m, "v": self.v, "master": self.master if self.master_weights else None,
-                "rank": self.fsdp.rank, "world": self.fsdp.world, "lr": self.lr, "betas": (self.b1, self.b2),
-                "eps": self.eps, "wd": self.wd}
-
     def load_state_dict(self, sd):
-        if sd.get("world", self.fsdp.world) != self.fsdp.world:
-            raise ValueError("sharded optimizer state was saved with a different world size")
-        self.step_count = sd["step"]
-        self.m.copy_(sd["m"])
-        self.v.copy_(sd["v"])
+        self._load_moments(sd)
         if self.master_weights and sd.get("master") is not None:
-            self.master.copy_(sd["master"])
+            self._master.copy_(sd["master"])
             with torch.no_grad():
-                self.fsdp.local_data.copy_(self.master.to(self.fsdp.dtype))
+                self.fsdp.local_data.copy_(self._master.to(self.fsdp.dtype))
             self.fsdp.mark_stale()
 
 

@@ -10,25 +10,88 @@ Master format (``master_format``): "split" (the GPU bf16 default) keeps only the
 each fp32 master beside the bf16 model weight, which holds the high half rounded (the pair
 reconstructs the master bit-exactly; ``ops.reference.split_master``): 26 instead of 28 B of HBM
 traffic per parameter per step and 2 B/param less memory. "fp32" keeps a separate fp32 master.
+
+Layering: ``adamw_update_`` updates one contiguous range (the only caller of the ``rca_adamw*``
+range kernels and of the CPU reference); ``AdamWBase`` holds what every AdamW here shares (state,
+step preamble, global norm, state dict); ``FlatAdamW`` (this file), ``ShardedAdamW`` (``fsdp.py``)
+and ``FullyShardedAdamW`` (``fully_sharded.py``) add their buffer layout and the loop over it.
 """
 from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
+import torch.distributed as dist
 
 from .. import ops
 from ..ops._lib import check, lib, stream_ptr
 from .flat import FlatParameters
 
 
-class FlatAdamW:
-    def __init__(self, flat: FlatParameters, lr: float = 3e-4, betas=(0.9, 0.95), eps: float = 1e-8,
-                 weight_decay: float = 0.1, max_grad_norm: Optional[float] = 1.0, master_weights: bool = True,
-                 lr_schedule=None, master_format: str = "auto"):
-        self.flat = flat
+class AdamWStep(NamedTuple):
+    """What one optimizer step hands to every ``adamw_update_`` of that step."""
+    lr: float
+    b1: float
+    b2: float
+    eps: float
+    bc1: float
+    bc2: float
+    step: int
+    grad_scale: float
+    clip: float            # max global grad norm, 0.0 = no clipping
+    sumsq: torch.Tensor    # [1] global sum of squared (unscaled) gradients; the kernels read it
+    cpu_coef: float        # the clip coefficient, taken on the host for CPU tensors only
+
+
+def _grad_dtype_code(g: torch.Tensor) -> int:
+    if g.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"unsupported grad dtype {g.dtype}")
+    return 0 if g.dtype == torch.bfloat16 else 1
+
+
+def adamw_update_(weights, grad, m, v, hp: AdamWStep, wd: float, *, master=None, lo=None, stream=None):
+    """One AdamW update of a contiguous range, given as equal-length 1-D views.
+
+    ``lo`` given: split master (``weights`` holds the bf16 high halves). ``master`` given: fp32
+    master, bf16 copy written to ``weights``. Neither: fp32 ``weights`` updated in place.
+    ``stream``: raw HIP stream (default: the current stream of the gradient's device)."""
+    n = grad.numel()
+    if any(t is not None and t.numel() != n for t in (weights, m, v, master, lo)):
+        raise ValueError("adamw_update_ needs views of equal length")  # a slice past a buffer's end is cut short
+    if n == 0:
+        return
+    if grad.is_cuda:
+        rest = (grad.data_ptr(), _grad_dtype_code(grad), m.data_ptr(), v.data_ptr(), n, hp.lr, hp.b1, hp.b2, hp.eps,
+                wd, hp.bc1, hp.bc2, hp.grad_scale, hp.sumsq.data_ptr() if hp.clip else 0, float(hp.clip),
+                stream_ptr(grad.device) if stream is None else stream)
+        if lo is not None:
+            check(lib().rca_adamw_split(weights.data_ptr(), lo.data_ptr(), *rest), "adamw_split")
+        elif master is not None:
+            check(lib().rca_adamw(master.data_ptr(), weights.data_ptr(), *rest), "adamw")
+        else:
+            check(lib().rca_adamw(weights.data_ptr(), 0, *rest), "adamw")
+        return
+    p = ops.reference.join_master(weights, lo) if lo is not None else (weights if master is None else master)
+    ops.reference.adamw_ref(p, grad, m, v, hp.lr, hp.b1, hp.b2, hp.eps, wd, hp.step, grad_mul=hp.grad_scale,
+                            clip=hp.cpu_coef)
+    if lo is not None:
+        hi, lo_ = ops.reference.split_master(p)
+        weights.copy_(hi)
+        lo.copy_(lo_)
+    elif master is not None:
+        weights.copy_(master.to(weights.dtype))
+
+
+class AdamWBase:
+    """State and step preamble shared by the flat, ZeRO and fully sharded AdamW. A subclass sets
+    its layout attributes, then calls ``__init__`` with the weights it owns (one 1-D tensor), and
+    sets ``_shard`` to its data-parallel wrapper (rank, world, pg) if its state is a shard."""
+    _shard = None
+
+    def __init__(self, weights: torch.Tensor, lr, betas, eps, weight_decay, max_grad_norm, lr_schedule,
+                 master_weights: bool = True, master_format: str = "fp32"):
         self.lr = lr
         self.b1, self.b2 = betas
         self.eps = eps
@@ -36,14 +99,90 @@ class FlatAdamW:
         self.max_grad_norm = max_grad_norm
         self.lr_schedule = lr_schedule
         self.step_count = 0
-        dev = flat.device
-        self.master_weights = master_weights and flat.dtype != torch.float32
-        self.split_master = _use_split(master_format, self.master_weights, flat.data)
-        self.lo = torch.zeros(flat.numel, dtype=torch.int16, device=dev) if self.split_master else None
-        self._master = None if self.split_master else (flat.data.float() if self.master_weights else flat.data)
-        self.m = torch.zeros(flat.numel, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(flat.numel, dtype=torch.float32, device=dev)
+        n, dev = weights.numel(), weights.device
+        self.master_weights = master_weights and weights.dtype != torch.float32
+        self.split_master = _use_split(master_format, self.master_weights, weights)
+        self.lo = torch.zeros(n, dtype=torch.int16, device=dev) if self.split_master else None
+        self._master = None if self.split_master else (weights.float() if self.master_weights else weights)
+        self.m = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(n, dtype=torch.float32, device=dev)
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._grad_scale = 1.0
+
+    @property
+    def param_groups(self):  # minimal torch.optim compatibility for LR schedulers / logging
+        return [{"lr": self.lr, "weight_decay": self.wd}]
+
+    def current_lr(self) -> float:
+        return self.lr_schedule(self.step_count) if self.lr_schedule else self.lr
+
+    @property
+    def clip(self) -> float:
+        return self.max_grad_norm if self.max_grad_norm and self.max_grad_norm > 0 else 0.0
+
+    def _owned_weights(self) -> torch.Tensor:
+        """The model-dtype weights this optimizer updates, in the order of ``m`` / ``v``."""
+        raise NotImplementedError
+
+    @property
+    def master(self) -> torch.Tensor:
+        """fp32 master of the owned elements (split format: reconstructed, a fresh tensor)."""
+        if self.split_master:
+            return ops.reference.join_master(self._owned_weights(), self.lo)
+        return self._master
+
+    def _global_sumsq(self, grads, pg=None, world: int = 1):
+        """Sum of squares of ``grads`` over all ranks into ``_sumsq`` (no host sync)."""
+        ops.grad_sumsq(grads, out=self._sumsq)
+        if world > 1:
+            dist.all_reduce(self._sumsq, group=pg)
+
+    def _begin_step(self, grad_scale: float) -> AdamWStep:
+        """Bump the step and fix its scalars; call once ``_sumsq`` holds this step's norm (when
+        clipping). Only a CPU ``_sumsq`` is read here: the GPU kernels read it on the device."""
+        self._grad_scale = grad_scale
+        self.step_count += 1
+        t = self.step_count
+        clip, coef = self.clip, 1.0
+        if clip and not self._sumsq.is_cuda:
+            nrm = math.sqrt(float(self._sumsq)) * abs(grad_scale)
+            coef = min(1.0, clip / (nrm + 1e-6))
+        return AdamWStep(self.current_lr(), self.b1, self.b2, self.eps, 1.0 - self.b1 ** t, 1.0 - self.b2 ** t, t,
+                         grad_scale, clip, self._sumsq, coef)
+
+    def _update(self, weights, grad, a: int, b: int, wd: float, hp: AdamWStep, stream=None):
+        """``adamw_update_`` of optimizer state [a, b) against equal-length weight / grad views."""
+        master = self._master[a:b] if self.master_weights and not self.split_master else None
+        lo = self.lo[a:b] if self.split_master else None
+        adamw_update_(weights, grad, self.m[a:b], self.v[a:b], hp, wd, master=master, lo=lo, stream=stream)
+
+    def grad_norm(self) -> float:
+        """Global grad norm of the last step (host sync — call only for logging)."""
+        return math.sqrt(float(self._sumsq.item())) * abs(self._grad_scale)
+
+    def state_dict(self):
+        """The optimizer state (for a sharded optimizer: this rank's shard, one file per rank)."""
+        sd = {"step": self.step_count, "m": self.m, "v": self.v, "master": self.master if self.master_weights else None}
+        if self._shard is not None:
+            sd.update(rank=self._shard.rank, world=self._shard.world)
+        sd.update(lr=self.lr, betas=(self.b1, self.b2), eps=self.eps, wd=self.wd)
+        return sd
+
+    def _load_moments(self, sd):
+        if self._shard is not None and sd.get("world", self._shard.world) != self._shard.world:
+            raise ValueError("sharded optimizer state was saved with a different world size")
+        self.step_count = sd["step"]
+        self.m.copy_(sd["m"])
+        self.v.copy_(sd["v"])
+
+
+class FlatAdamW(AdamWBase):
+    def __init__(self, flat: FlatParameters, lr: float = 3e-4, betas=(0.9, 0.95), eps: float = 1e-8,
+                 weight_decay: float = 0.1, max_grad_norm: Optional[float] = 1.0, master_weights: bool = True,
+                 lr_schedule=None, master_format: str = "auto"):
+        self.flat = flat
+        super().__init__(flat.data, lr, betas, eps, weight_decay, max_grad_norm, lr_schedule, master_weights,
+                         master_format)
         self.last_grad_norm = None  # device tensor (sum of squares, pre-scale)
         self.track_grad_norm = False
         self._ov = None  # forward-overlap state (overlap_with_forward)
@@ -111,19 +250,8 @@ class FlatAdamW:
             ov["done"] = None
             ov["events"] = [None] * len(self.flat.buckets)
 
-    @property
-    def param_groups(self):  # minimal torch.optim compatibility for LR schedulers / logging
-        return [{"lr": self.lr, "weight_decay": self.wd}]
-
-    def current_lr(self) -> float:
-        return self.lr_schedule(self.step_count) if self.lr_schedule else self.lr
-
-    @property
-    def master(self) -> torch.Tensor:
-        """The fp32 master weights (with the split format: reconstructed, a fresh tensor)."""
-        if self.split_master:
-            return ops.reference.join_master(self.flat.data, self.lo)
-        return self._master
+    def _owned_weights(self) -> torch.Tensor:
+        return self.flat.data
 
     def _setup_transposed(self):
         """W^T buffers for the fused-wgrad linear weights + the segment table of the update.
@@ -176,103 +304,54 @@ class FlatAdamW:
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
-        self.step_count += 1
-        t = self.step_count
-        lr = self.current_lr()
-        bc1 = 1.0 - self.b1 ** t
-        bc2 = 1.0 - self.b2 ** t
         flat = self.flat
         flat.finalize_fresh()
         g = flat.step_grad
-        clip = self.max_grad_norm if self.max_grad_norm and self.max_grad_norm > 0 else 0.0
         pre, flat.precomputed_sumsq = flat.precomputed_sumsq, None
-        if clip or self.track_grad_norm:
+        if self.clip or self.track_grad_norm:
             if pre is not None and pre.device == self._sumsq.device:
                 self._sumsq.copy_(pre)  # taken during backward (DistributedDataParallel precompute_grad_norm)
             else:
-                ops.grad_sumsq([g], out=self._sumsq)
+                self._global_sumsq([g])
             self.last_grad_norm = self._sumsq  # sqrt taken lazily by grad_norm()
-        self._grad_scale = grad_scale
-        segs = [(0, flat.decay_end, self.wd), (flat.decay_end, flat.numel, 0.0)]
+        hp = self._begin_step(grad_scale)
         self._wt_epoch[0] += 1  # every update changes W: W^T is stale unless refreshed below
-        if g.is_cuda:
-            if g.dtype not in (torch.bfloat16, torch.float32):
-                raise TypeError(f"unsupported grad dtype {g.dtype}")
-            ov = self._ov
-            if ov is None and self.transposed_weights:
-                if self._segs is None:
-                    self._setup_transposed()
-                check(lib().rca_adamw_split_seg(
-                    flat.data.data_ptr(), self.lo.data_ptr(), g.data_ptr(), 0 if g.dtype == torch.bfloat16 else 1,
-                    self.m.data_ptr(), self.v.data_ptr(), self._segs.data_ptr(), self._segs.shape[0],
-                    self._seg_blocks, lr, self.b1, self.b2, self.eps, self.wd, bc1, bc2, grad_scale,
-                    self._sumsq.data_ptr() if clip else 0, float(clip), stream_ptr(g.device)), "adamw_split_seg")
-                ep = self._wt_epoch[0]
-                for p in self._wt_params:
-                    p._rca_wt_key = (p._version, ep)
-                return
-            if ov is None:
-                for s, e, wd in segs:
-                    self._launch(g, s, e, wd, lr, bc1, bc2, grad_scale, clip, stream_ptr(g.device))
-                return
-            # overlapped: the side stream starts once the gradients (and their norm) are final
-            self.wait_pending_update()
-            main = torch.cuda.current_stream(g.device)
-            side = ov["stream"]
-            side.wait_stream(main)
-            sp = side.cuda_stream
-            for bi in ov["order"]:
-                b = flat.buckets[bi]
-                wd = self.wd if b.start < flat.decay_end else 0.0
-                self._launch(g, b.start, min(b.end, flat.numel), wd, lr, bc1, bc2, grad_scale, clip, sp)
-                ev = ov["evs"][bi]
-                ev.record(side)
-                ov["events"][bi] = ev
-            ov["done_ev"].record(side)
-            ov["done"] = ov["done_ev"]
-            ov["pending_zero"] = True
-        else:
-            coef = 1.0
-            if clip:
-                nrm = math.sqrt(float(self._sumsq)) * abs(grad_scale)
-                coef = min(1.0, clip / (nrm + 1e-6))
-            master = self.master
-            for s, e, wd in segs:
-                if e <= s:
-                    continue
-                ops.reference.adamw_ref(master[s:e], g[s:e], self.m[s:e], self.v[s:e], lr, self.b1, self.b2,
-                                        self.eps, wd, t, grad_mul=grad_scale, clip=coef)
-            if self.split_master:
-                hi, lo = ops.reference.split_master(master)
-                flat.data.copy_(hi)
-                self.lo.copy_(lo)
-            elif self.master_weights:
-                flat.data.copy_(master.to(flat.dtype))
-
-    def _launch(self, g, s, e, wd, lr, bc1, bc2, grad_scale, clip, st):
-        n = e - s
-        if n <= 0:
+        ov = self._ov  # None on CPU
+        if ov is None and self.transposed_weights:
+            gdt = _grad_dtype_code(g)
+            if self._segs is None:
+                self._setup_transposed()
+            check(lib().rca_adamw_split_seg(
+                flat.data.data_ptr(), self.lo.data_ptr(), g.data_ptr(), gdt,
+                self.m.data_ptr(), self.v.data_ptr(), self._segs.data_ptr(), self._segs.shape[0],
+                self._seg_blocks, hp.lr, self.b1, self.b2, self.eps, self.wd, hp.bc1, hp.bc2, grad_scale,
+                self._sumsq.data_ptr() if hp.clip else 0, float(hp.clip), stream_ptr(g.device)), "adamw_split_seg")
+            ep = self._wt_epoch[0]
+            for p in self._wt_params:
+                p._rca_wt_key = (p._version, ep)
             return
-        flat = self.flat
-        gdt = 0 if g.dtype == torch.bfloat16 else 1
-        if self.split_master:
-            check(lib().rca_adamw_split(flat.data.data_ptr() + s * 2, self.lo.data_ptr() + s * 2,
-                                        g.data_ptr() + s * g.element_size(), gdt, self.m.data_ptr() + s * 4,
-                                        self.v.data_ptr() + s * 4, n, lr, self.b1, self.b2, self.eps, wd, bc1, bc2,
-                                        grad_scale, self._sumsq.data_ptr() if clip else 0, float(clip), st),
-                  "adamw_split")
+        if ov is None:
+            for s, e, wd in ((0, flat.decay_end, self.wd), (flat.decay_end, flat.numel, 0.0)):
+                self._update(flat.data[s:e], g[s:e], s, e, wd, hp)
             return
-        p16 = flat.data.data_ptr() + s * flat.data.element_size() if self.master_weights else 0
-        check(lib().rca_adamw(self._master.data_ptr() + s * self._master.element_size(), p16,
-                              g.data_ptr() + s * g.element_size(), gdt, self.m.data_ptr() + s * 4,
-                              self.v.data_ptr() + s * 4, n, lr, self.b1, self.b2, self.eps, wd, bc1, bc2, grad_scale,
-                              self._sumsq.data_ptr() if clip else 0, float(clip), st), "adamw")
+        # overlapped: the side stream starts once the gradients (and their norm) are final
+        self.wait_pending_update()
+        main = torch.cuda.current_stream(g.device)
+        side = ov["stream"]
+        side.wait_stream(main)
+        for bi in ov["order"]:
+            b = flat.buckets[bi]
+            s, e = b.start, min(b.end, flat.numel)
+            self._update(flat.data[s:e], g[s:e], s, e, self.wd if s < flat.decay_end else 0.0, hp, side.cuda_stream)
+            ev = ov["evs"][bi]
+            ev.record(side)
+            ov["events"][bi] = ev
+        ov["done_ev"].record(side)
+        ov["done"] = ov["done_ev"]
+        ov["pending_zero"] = True
 
     def grad_norm(self) -> float:
-        """Global grad norm of the last step (host sync — call only for logging)."""
-        if self.last_grad_norm is None:
-            return 0.0
-        return math.sqrt(float(self.last_grad_norm.item())) * abs(getattr(self, "_grad_scale", 1.0))
+        return super().grad_norm() if self.last_grad_norm is not None else 0.0
 
     def zero_grad(self, set_to_none: bool = False):
         ov = self._ov
@@ -288,14 +367,11 @@ class FlatAdamW:
 
     def state_dict(self):
         self.wait_pending_update()
-        return {"step": self.step_count, "m": self.m, "v": self.v, "master": self.master if self.master_weights else None,
-                "lr": self.lr, "betas": (self.b1, self.b2), "eps": self.eps, "wd": self.wd}
+        return super().state_dict()
 
     def load_state_dict(self, sd):
         self._wt_epoch[0] += 1
-        self.step_count = sd["step"]
-        self.m.copy_(sd["m"])
-        self.v.copy_(sd["v"])
+        self._load_moments(sd)
         if self.master_weights and sd.get("master") is not None:
             if self.split_master:
                 hi, lo = ops.reference.split_master(sd["master"].to(self.flat.device))

@@ -397,10 +397,12 @@ def test_vtrace_kernel_matches_reference():
     assert torch.allclose(pg.cpu(), pg_r, atol=1e-4, rtol=1e-4)
 
 
+@pytest.mark.parametrize("master_format", ["auto", "fp32"])
 @pytest.mark.parametrize("clip", [None, 0.5])
-def test_sharded_adamw_matches_flat_adamw_gpu(clip):
+def test_sharded_adamw_matches_flat_adamw_gpu(clip, master_format):
     """world=1 ZeRO optimizer path (per-bucket chunks, HIP AdamW per chunk) == the flat AdamW path,
-    fed identical gradients (the model's backward has atomics, so grads are fed, not recomputed)."""
+    fed identical gradients (the model's backward has atomics, so grads are fed, not recomputed).
+    "auto" is the split master (flat: the segmented W^T-writing launch), "fp32" a separate master."""
     from ray_community_amd.models import build_llama
     from ray_community_amd.parallel import DistributedDataParallel, FlatAdamW, ShardedAdamW, ShardedDataParallel
 
@@ -409,8 +411,8 @@ def test_sharded_adamw_matches_flat_adamw_gpu(clip):
     torch.manual_seed(0)
     w2 = ShardedDataParallel(build_llama("llama3-tiny", device=DEV), bucket_cap_mb=0.2)
     assert w1.flat.offsets == w2.flat.offsets and len(w2.flat.buckets) > 2
-    o1 = FlatAdamW(w1.flat, lr=1e-3, max_grad_norm=clip)
-    o2 = ShardedAdamW(w2, lr=1e-3, max_grad_norm=clip)
+    o1 = FlatAdamW(w1.flat, lr=1e-3, max_grad_norm=clip, master_format=master_format)
+    o2 = ShardedAdamW(w2, lr=1e-3, max_grad_norm=clip, master_format=master_format)
     g = torch.Generator(device=DEV)
     g.manual_seed(1)
     for _ in range(3):
