@@ -20,8 +20,9 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from .. import ops
 from .kv_cache import PagedKVCache
-from .llama import _seeded_generator, sample_tokens
+from .llama import _seeded_generator, sample_tokens, use_fused_sampling
 
 
 @dataclass
@@ -44,6 +45,12 @@ class _Request:
     prefix: Optional["_Prefix"] = None              # held until the prefill is over
     forked: bool = False
     shared: int = 0                                 # blocks shared with the prefix (not in ``blocks``)
+    # batched sampler (ops.sample_logits): stepped by ``produced``, so the stream is a function of
+    # the seed and the request's own logits, never of its slot or its neighbours
+    top_p: float = 1.0
+    min_p: float = 0.0
+    seed: int = 0
+    fused: bool = False
 
 
 @dataclass
@@ -63,10 +70,11 @@ _NO_LIMIT = 1 << 62
 
 class GenerationEngine:
     def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8, num_blocks: int = 256,
-                 page_size: int = 16, prefill_chunk: Optional[int] = None):
+                 page_size: int = 16, prefill_chunk: Optional[int] = None, fused_sampling: bool = False):
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
+        self.fused_sampling = bool(fused_sampling)
         self._prefixes = {}
         self.model = model
         w = model.embed.weight
@@ -114,11 +122,18 @@ class GenerationEngine:
             self._drop_prefix_if_unused(pfx)
 
     def add_request(self, prompt, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
-                    seed=None, prefix: Optional[int] = None) -> int:
+                    seed=None, prefix: Optional[int] = None, top_p: float = 1.0, min_p: float = 0.0) -> int:
         """Queue a request; returns its id. It is admitted by a later ``step()`` once a slot is
         free and the cache can hold its whole sequence (prompt + ``max_new_tokens``). With
         ``prefix`` (a ``register_prefix`` handle) ``prompt`` is the suffix after that prefix: the
-        request shares the prefix's whole cache pages and needs blocks only for the rest."""
+        request shares the prefix's whole cache pages and needs blocks only for the rest.
+
+        ``top_p`` / ``min_p`` (``ops.sample_logits``) or the engine's ``fused_sampling`` put the
+        request on the batched sampler: all such rows of a step's logits are sampled by one call,
+        each with ``seed`` (0 if ``None``) and its own count of produced tokens as the step."""
+        fused = use_fused_sampling(self.fused_sampling, top_p, min_p)
+        ops.check_sampling_params([float(temperature)] if fused else [], [int(top_k)] if fused else [],
+                                  [float(top_p)], [float(min_p)])
         prompt = [int(t) for t in prompt]
         if not prompt or max_new_tokens < 1:
             raise ValueError("a request needs a non-empty prompt and max_new_tokens >= 1")
@@ -143,7 +158,8 @@ class GenerationEngine:
         gen = _seeded_generator(self.model.embed.weight.device, temperature, seed)
         rid = next(self._ids)
         req = _Request(rid, prompt, int(max_new_tokens), float(temperature), int(top_k), eos_token_id, gen, blocks,
-                       seq_id=("engine", id(self), rid))
+                       seq_id=("engine", id(self), rid), top_p=float(top_p), min_p=float(min_p),
+                       seed=0 if seed is None else int(seed), fused=fused)
         if pfx is not None:
             req.prefix = pfx
             pfx.users += 1
@@ -186,8 +202,29 @@ class GenerationEngine:
         return own + sum(p.blocks - self.cache.blocks_held(p.seq_id) for p in pfx.values())
 
     # ------------------------------------------------------------------------------------ step
-    def _emit(self, req: _Request, logits_row, events) -> bool:
-        tok = int(self._sample(logits_row[None], req.temperature, req.top_k, req.generator)[0])
+    def _tokens(self, logits, picks):
+        """The next token of every ``(request, row of logits)`` in ``picks``: the fused requests
+        through one ``ops.sample_logits`` call and one host copy, the others one by one."""
+        toks = [None] * len(picks)
+        fused = [n for n, (req, _) in enumerate(picks) if req.fused]
+        if fused:
+            rows = [picks[n][1] for n in fused]
+            reqs = [picks[n][0] for n in fused]
+            if rows != list(range(logits.shape[0])):
+                logits_f = logits[torch.tensor(rows, dtype=torch.long, device=logits.device)]
+            else:
+                logits_f = logits
+            out = ops.sample_logits(logits_f, [r.temperature for r in reqs], [r.top_k for r in reqs],
+                                    [r.top_p for r in reqs], [r.min_p for r in reqs], [r.seed for r in reqs],
+                                    [r.produced for r in reqs]).tolist()
+            for n, tok in zip(fused, out):
+                toks[n] = int(tok)
+        for n, (req, row) in enumerate(picks):
+            if not req.fused:
+                toks[n] = int(self._sample(logits[row][None], req.temperature, req.top_k, req.generator)[0])
+        return toks
+
+    def _emit(self, req: _Request, tok: int, events) -> bool:
         req.produced += 1
         req.last = tok
         finished = req.produced >= req.max_new_tokens or (req.eos_token_id is not None and tok == req.eos_token_id)
@@ -238,14 +275,15 @@ class GenerationEngine:
         except Exception:
             self._requeue([slot for slot, _, _ in items if slot is not None])
             raise
-        done = set()
+        done, emit = set(), []
         for i, (slot, obj, toks) in enumerate(items):
             obj.fed += len(toks)
-            if slot is None or obj.fed < len(obj.feed):
-                continue
+            if slot is not None and obj.fed >= len(obj.feed):
+                emit.append((slot, obj, i))
+        for (slot, obj, _), tok in zip(emit, self._tokens(logits, [(obj, i) for _, obj, i in emit])):
             obj.prefilling = False
             self._unhold_prefix(obj)
-            if self._emit(obj, logits[i], events):
+            if self._emit(obj, tok, events):
                 self._retire(slot)
             else:
                 done.add(obj.rid)
@@ -296,8 +334,9 @@ class GenerationEngine:
             seq_ids = [r.seq_id if on else None for r, on in zip(self.slots, live)]
             tokens = [r.last if on else 0 for r, on in zip(self.slots, live)]
             logits = self.model.decode_step(tokens, self.cache, seq_ids)
-            for slot, req in enumerate(self.slots):
-                if live[slot] and self._emit(req, logits[slot], events):
+            picks = [(req, slot) for slot, req in enumerate(self.slots) if live[slot]]
+            for (req, slot), tok in zip(picks, self._tokens(logits, picks)):
+                if self._emit(req, tok, events):
                     self._retire(slot)
 
     def step(self) -> List[Tuple[int, int, bool]]:

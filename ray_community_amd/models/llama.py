@@ -354,16 +354,27 @@ class Llama(nn.Module):
 
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
-                 seed=None, cache=None, prefill_chunk=None):
+                 seed=None, cache=None, prefill_chunk=None, top_p: float = 1.0, min_p: float = 0.0,
+                 fused_sampling: bool = False):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
         stops after emitting ``eos_token_id``. ``cache``: a ``PagedKVCache`` to use (its blocks are
         released on exit); by default one just large enough is made. ``prefill_chunk``: feed the
         prompts through ``extend``, at most that many tokens per sequence per call, instead of
-        one ``prefill``."""
+        one ``prefill``.
+
+        ``top_p`` (nucleus) and ``min_p`` restrict the sampled set further (``ops.sample_logits``
+        has the exact rules). They, or ``fused_sampling=True``, select the batched sampler: one
+        ``ops.sample_logits`` call per step over all rows, every row seeded with ``seed`` (0 if
+        ``None``) and stepped by the number of tokens produced so far, so a row's tokens are a
+        function of ``seed`` and its own logits only. Without any of the three the
+        ``sample_tokens`` path runs, with the token streams it always gave."""
         from .kv_cache import PagedKVCache
 
+        fused = use_fused_sampling(fused_sampling, top_p, min_p)
+        if fused:
+            ops.check_sampling_params([float(temperature)], [int(top_k)], [float(top_p)], [float(min_p)])
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         prompts = [list(p) for p in prompts]
@@ -386,7 +397,11 @@ class Llama(nn.Module):
             else:
                 logits = self._chunked_prefill(prompts, cache, ids, int(prefill_chunk))
             for step in range(max_new_tokens):
-                nxt = sample_tokens(logits, temperature, top_k, gen).tolist()
+                if fused:
+                    nxt = ops.sample_logits(logits, temperature, top_k, top_p, min_p, 0 if seed is None else int(seed),
+                                            step).tolist()
+                else:
+                    nxt = sample_tokens(logits, temperature, top_k, gen).tolist()
                 for b, sid in enumerate(active):
                     if sid is None:
                         continue
@@ -425,6 +440,13 @@ def _seeded_generator(device, temperature, seed):
     gen = torch.Generator(device=device)
     gen.manual_seed(0 if seed is None else int(seed))
     return gen
+
+
+def use_fused_sampling(fused_sampling, top_p, min_p) -> bool:
+    """Whether a request samples through ``ops.sample_logits``: on demand, or because it sets
+    ``top_p`` or ``min_p``, which only that sampler implements. Out-of-range values also go there,
+    to be refused by its checks."""
+    return bool(fused_sampling) or not float(top_p) == 1.0 or not float(min_p) == 0.0
 
 
 def sample_tokens(logits, temperature: float = 0.0, top_k: int = 0, generator=None):

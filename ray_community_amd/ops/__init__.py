@@ -40,6 +40,8 @@ __all__ = [
     "kv_cache_append_",
     "paged_attention_decode",
     "paged_attention_extend",
+    "sample_logits",
+    "sample_logits_supported",
     "kernels_available",
 ]
 
@@ -1209,4 +1211,117 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
                                       block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
                                       out.data_ptr(), B, max_q_len, Hq, Hk, D, page, block_table.shape[1], num_blocks,
                                       scale, stream_ptr(q.device)), "rca_attn_extend_paged")
+    return out
+
+
+# ---------------------------------------------------------------------------------- sampling
+_SAMPLE_MAX_V = 1 << 20
+
+
+def sample_logits_supported(logits) -> bool:
+    """Whether the gfx950 sampling kernel takes these logits (otherwise: the reference)."""
+    return (logits.dim() == 2 and logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float32)
+            and 1 <= logits.shape[1] <= _SAMPLE_MAX_V and logits.shape[0] <= 65535
+            and (logits.stride(1) == 1 or logits.shape[1] == 1) and logits.stride(0) >= 0)
+
+
+def _per_row(name, value, B, kind):
+    """``value`` (a scalar, a sequence of ``B`` or a tensor of ``B``) as a list of ``B`` ``kind``s."""
+    if torch.is_tensor(value):
+        value = value.detach().cpu().reshape(-1).tolist() if value.dim() else value.item()
+    if isinstance(value, (list, tuple)):
+        if len(value) != B:
+            raise ValueError(f"{name} has {len(value)} values for {B} rows of logits")
+        vals = list(value)
+    else:
+        vals = [value] * B
+    try:
+        return [kind(v) for v in vals]
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{name} must hold {kind.__name__} values, got {value!r}") from None
+
+
+def check_sampling_params(temperature, top_k, top_p, min_p):
+    """Raise ``ValueError`` naming the first sampling parameter (lists of per-row values) out of range."""
+    import math
+
+    for t in temperature:
+        if not (math.isfinite(t) and t >= 0):
+            raise ValueError(f"temperature must be finite and >= 0, got {t!r}")
+    for k in top_k:
+        if k < 0:
+            raise ValueError(f"top_k must be >= 0, got {k!r}")
+    for p in top_p:
+        if not 0 < p <= 1:
+            raise ValueError(f"top_p must be in (0, 1], got {p!r}")
+    for p in min_p:
+        if not 0 <= p <= 1:
+            raise ValueError(f"min_p must be in [0, 1], got {p!r}")
+
+
+def sample_logits(logits, temperature, top_k=0, top_p=1.0, min_p=0.0, seeds=0, steps=0, uniforms=None):
+    """Next token per row of ``logits`` ``[B, V]`` in one launch; returns int64 ``[B]``.
+
+    ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``seeds`` and ``steps`` are each a scalar, a
+    sequence of ``B`` or a tensor of ``B`` (floats travel as fp32, seeds and steps modulo 2**64).
+    Per row, with logits ``x``:
+      * ``temperature == 0`` is greedy: the lowest index attaining the maximum; the rest is ignored.
+      * Otherwise ``w_i = exp((x_i - max x) / temperature)`` in fp32 from the stored logit. A token
+        is kept if it passes all three tie-inclusive filters (the kept set never depends on an
+        ordering of equal logits): ``top_k > 0``: ``x_i >=`` the ``top_k``-th largest value (0 or
+        ``>= V`` keeps all); ``top_p < 1``: among the ``top_k`` survivors, the total ``w`` of
+        survivors with a larger logit is below ``top_p`` times the survivors' total (the smallest
+        prefix of the descending order reaching mass ``top_p``, plus ties); ``min_p > 0``:
+        ``w_i >= min_p``, i.e. probability at least ``min_p`` times the maximum one.
+      * With ``C`` the kept total, the token is the smallest kept index, in vocabulary order, whose
+        inclusive running sum of kept ``w`` exceeds ``u * C`` (the last kept index if rounding
+        leaves none).
+      * ``u = ((r >> 8) + 0.5) * 2**-24`` with ``r`` word 0 of Philox4x32-10 at counter
+        ``(step & 0xffffffff, step >> 32, 0, 0)`` and key ``(seed & 0xffffffff, seed >> 32)``:
+        strictly inside (0, 1), a function of (seed, step) only, and carried in float64 (its 25
+        significant bits are one more than fp32 holds; ``reference.philox_uniforms``). ``uniforms``
+        (``[B]``, used as fp32) replaces it.
+    A row's token is a bitwise-reproducible function of that row's inputs alone: not of ``B``, the
+    row's place in the batch, the other rows or the run. Rows with a NaN or without a finite logit
+    are out of contract; they still give an index in ``[0, V)``.
+
+    The gfx950 kernel takes bf16 or fp32 logits on the GPU with unit inner stride (any row stride),
+    ``1 <= V <= 2**20`` and ``B <= 65535`` (``sample_logits_supported``); anything else runs
+    ``reference.sample_logits_ref``. A call costs one small host-to-device copy of the packed
+    parameters and one launch; ``B == 0`` returns an empty tensor without a launch."""
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise ValueError(f"logits must be a 2-D tensor [B, V], got "
+                         f"{tuple(logits.shape) if torch.is_tensor(logits) else type(logits).__name__}")
+    B, V = logits.shape
+    temperature = _per_row("temperature", temperature, B, float)
+    top_k = _per_row("top_k", top_k, B, int)
+    top_p = _per_row("top_p", top_p, B, float)
+    min_p = _per_row("min_p", min_p, B, float)
+    seeds = _per_row("seeds", seeds, B, int)
+    steps = _per_row("steps", steps, B, int)
+    check_sampling_params(temperature, top_k, top_p, min_p)
+    if uniforms is not None:
+        if not torch.is_tensor(uniforms) or uniforms.dim() != 1 or uniforms.shape[0] != B:
+            raise ValueError(f"uniforms must be a tensor of {B} values")
+    if B == 0:
+        return torch.empty(0, dtype=torch.int64, device=logits.device)
+    if V < 1:
+        raise ValueError("logits must have at least one column")
+    if not sample_logits_supported(logits):
+        return ref.sample_logits_ref(logits, temperature, top_k, top_p, min_p, seeds, steps, uniforms)
+    import numpy as np
+
+    packed = np.empty((B, 8), dtype=np.int32)
+    f32 = np.array([temperature, top_p, min_p], dtype=np.float32).view(np.int32)
+    packed[:, 0], packed[:, 2], packed[:, 3] = f32[0], f32[1], f32[2]
+    packed[:, 1] = np.minimum(np.array(top_k, dtype=np.int64), V)
+    packed[:, 4:6] = ref._u64_array(seeds).view(np.int32).reshape(B, 2)  # little endian: low word first
+    packed[:, 6:8] = ref._u64_array(steps).view(np.int32).reshape(B, 2)
+    params = torch.from_numpy(packed).to(logits.device)
+    if uniforms is not None:
+        uniforms = uniforms.to(device=logits.device, dtype=torch.float32).contiguous()
+    out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    check(lib().rca_sample_logits(logits.data_ptr(), logits.stride(0), 1 if logits.dtype == torch.bfloat16 else 0,
+                                  params.data_ptr(), _p(uniforms), out.data_ptr(), B, V, stream_ptr(logits.device)),
+          "rca_sample_logits")
     return out

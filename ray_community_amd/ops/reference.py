@@ -227,3 +227,117 @@ def paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, c
         p = torch.nan_to_num(p)  # a query before position 0 sees nothing: zeros
         out[q0:q1] = torch.einsum("hin,nhd->ihd", p, v).reshape(n, Hq * D)
     return out.to(q.dtype)
+
+
+# ------------------------------------------------------------------------------------ sampling
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on numpy uint64 arrays holding 32-bit words: ``counter`` is four arrays,
+    ``key`` two; returns the four output words."""
+    import numpy as np
+
+    mask = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & mask for c in counter)
+    k0, k1 = (np.asarray(k, dtype=np.uint64) & mask for k in key)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2  # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & mask, (k1 + np.uint64(_PHILOX_W1)) & mask
+    return c0, c1, c2, c3
+
+
+def _u64_array(values):
+    """``values`` (ints of any sign or size, a sequence or a tensor of them) as numpy uint64, mod 2**64."""
+    import numpy as np
+
+    if torch.is_tensor(values):
+        values = values.detach().cpu().reshape(-1).tolist()
+    return np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in values], dtype=np.uint64)
+
+
+def philox_uniforms(seeds, steps):
+    """The sampler's random number per row, float64 ``[B]`` on the CPU: ``u = ((r >> 8) + 0.5) * 2**-24``
+    with ``r`` word 0 of Philox4x32-10 at counter ``(step & 0xffffffff, step >> 32, 0, 0)`` and key
+    ``(seed & 0xffffffff, (seed >> 32) & 0xffffffff)``. ``u`` lies strictly inside (0, 1) and depends
+    on nothing but (seed, step). It has 25 significant bits, one more than fp32 holds (rounded to
+    fp32 its top value would be 1.0), so it is kept, here and in the kernel, in float64, where it
+    is exact."""
+    import numpy as np
+
+    seeds, steps = _u64_array(seeds), _u64_array(steps)
+    zero = np.zeros_like(steps)
+    r = philox4x32_10((steps, steps >> np.uint64(32), zero, zero), (seeds, seeds >> np.uint64(32)))[0]
+    u = ((r >> np.uint64(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    return torch.from_numpy(u)
+
+
+def _f32(v) -> float:
+    """``v`` rounded to fp32 (the precision the sampler's per-row parameters travel in)."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def sample_kept_ref(x, temperature, top_k, top_p, min_p):
+    """One row of the sampler: the weights ``w = exp((x - max x) / temperature)`` (computed in fp32,
+    returned as float64) and the boolean kept set under the tie-inclusive ``top_k`` / ``top_p`` /
+    ``min_p`` filters of ``sample_logits_ref``. ``x``: 1-D logits; ``temperature > 0``."""
+    x = x.detach().float().cpu()
+    V = x.shape[0]
+    w32 = torch.exp((x - x.max()) / torch.tensor(_f32(temperature), dtype=torch.float32))
+    w = w32.double()
+    keep = torch.ones(V, dtype=torch.bool)
+    top_k = int(top_k)
+    if 0 < top_k < V:
+        keep &= x >= x.topk(top_k).values[-1]
+    if _f32(top_p) < 1.0:
+        # mass of the survivors strictly above each survivor, by distinct value
+        vals, inv = torch.unique(x[keep], return_inverse=True)  # ascending
+        mass = torch.zeros(vals.shape[0], dtype=torch.float64).index_add_(0, inv, w[keep])
+        above = mass.flip(0).cumsum(0).flip(0) - mass
+        ok = above[inv] < _f32(top_p) * mass.sum()
+        keep[keep.clone()] = ok
+    if _f32(min_p) > 0.0:
+        keep &= w32 >= torch.tensor(_f32(min_p), dtype=torch.float32)
+    return w, keep
+
+
+def sample_logits_ref(logits, temperature, top_k, top_p, min_p, seeds, steps, uniforms=None):
+    """Reference of ``ops.sample_logits``: next token per row of ``logits`` ``[B, V]``; every
+    parameter is a sequence (or tensor) of ``B`` values. Returns int64 ``[B]`` on ``logits.device``.
+
+    Per row, with logits ``x``: ``temperature == 0`` returns the lowest index attaining the maximum
+    and ignores the rest. Otherwise ``w_i = exp((x_i - max x) / temperature)`` in fp32 from the
+    stored logit, and a token is kept if it passes all of (each tie-inclusive, so the kept set
+    does not depend on any ordering of equal logits):
+      * ``top_k > 0``: ``x_i >=`` the ``top_k``-th largest value (0 or ``>= V``: all);
+      * ``top_p < 1``: among the ``top_k`` survivors, with ``S_i`` the total ``w`` of survivors with
+        ``x_j > x_i`` and ``W`` the survivors' total, ``S_i < top_p * W`` (the smallest prefix of
+        the descending order reaching mass ``top_p``, plus ties);
+      * ``min_p > 0``: ``w_i >= min_p`` (probability at least ``min_p`` times the maximum one).
+    With ``C`` the total ``w`` of the kept set, the result is the smallest kept index, in
+    vocabulary order, whose inclusive running sum of kept ``w`` exceeds ``u * C`` (the last kept
+    index if rounding leaves none). ``u`` is ``uniforms[row]`` if given, else
+    ``philox_uniforms(seeds, steps)[row]``. Everything after the ``exp`` is float64 here.
+    Temperature, ``top_p`` and ``min_p`` are taken at fp32 precision. Rows with a NaN or without a
+    finite logit are out of contract."""
+    B, V = logits.shape
+    if uniforms is None:
+        uniforms = philox_uniforms(seeds, steps)
+    u = torch.as_tensor(uniforms).detach().double().cpu().reshape(-1)
+    x_all = logits.detach().float().cpu()
+    temperature, top_k, top_p, min_p = (v.detach().cpu().tolist() if torch.is_tensor(v) else list(v)
+                                         for v in (temperature, top_k, top_p, min_p))
+    out = torch.empty(B, dtype=torch.int64)
+    for b in range(B):
+        x = x_all[b]
+        if not temperature[b] > 0:
+            out[b] = int(torch.nonzero(x == x.max())[0]) if V else 0
+            continue
+        w, keep = sample_kept_ref(x, temperature[b], top_k[b], top_p[b], min_p[b])
+        w = w * keep
+        run = w.cumsum(0)
+        hit = torch.nonzero(keep & (run > u[b] * w.sum()))
+        out[b] = int(hit[0]) if hit.numel() else int(torch.nonzero(keep)[-1])
+    return out.to(logits.device)

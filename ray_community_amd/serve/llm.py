@@ -21,11 +21,13 @@ from .api import deployment
 class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
                  num_blocks: int = 256, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
-                 prefill_chunk=None):
+                 prefill_chunk=None, fused_sampling: bool = False):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
         ``torch.save``d state dict (without one the weights are initialised from ``seed``);
         ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
-        no longer pauses the running streams for its whole prefill); ``None`` prefills in one go."""
+        no longer pauses the running streams for its whole prefill); ``None`` prefills in one go;
+        ``fused_sampling``: every request samples through the engine's batched sampler
+        (``ops.sample_logits``: one launch a step) instead of only those that set ``top_p`` / ``min_p``."""
         import torch
 
         from ..models import GenerationEngine, build_llama
@@ -36,7 +38,7 @@ class _LlamaDeployment:
             self.model.load_state_dict(torch.load(state_dict_path, map_location=device))
         self.model.eval()
         self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
-                                       prefill_chunk=prefill_chunk)
+                                       prefill_chunk=prefill_chunk, fused_sampling=fused_sampling)
         self.default_max_new_tokens = int(default_max_new_tokens)
         # one model thread: the engine is not re-entrant, and per-thread GPU library state stays warm
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="llama-engine")
@@ -68,15 +70,16 @@ class _LlamaDeployment:
             self._driver = None
 
     async def generate(self, prompt_tokens, max_new_tokens=None, temperature: float = 0.0, top_k: int = 0,
-                       eos_token_id=None, seed=None):
-        """Async generator of the new token ids of one request."""
+                       eos_token_id=None, seed=None, top_p: float = 1.0, min_p: float = 0.0):
+        """Async generator of the new token ids of one request (sampling arguments as in
+        ``GenerationEngine.add_request``)."""
         loop = asyncio.get_running_loop()
         n = self.default_max_new_tokens if max_new_tokens is None else int(max_new_tokens)
         q = asyncio.Queue()
 
         def add():  # on the engine thread, so no step can run between queueing and registering
             rid = self.engine.add_request(list(prompt_tokens), n, temperature=temperature, top_k=top_k,
-                                          eos_token_id=eos_token_id, seed=seed)
+                                          eos_token_id=eos_token_id, seed=seed, top_p=top_p, min_p=min_p)
             self._queues[rid] = [q, n, 0]
             return rid
 
@@ -102,20 +105,23 @@ class _LlamaDeployment:
         """Engine occupancy and, per open stream, how far it is: ``{"active", "waiting", "streams":
         [{"request_id", "max_new_tokens", "produced"}], "cancelled"}``; a deployment with
         ``prefill_chunk`` set adds ``"prefill_chunk"`` and ``"prefilling"`` (requests still in
-        their prompt)."""
+        their prompt), one with ``fused_sampling`` adds ``"fused_sampling": True``."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
                    for rid, e in list(self._queues.items())]
         st = {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
               "cancelled": self._cancelled}
         if self.engine.prefill_chunk is not None:
             st.update(prefill_chunk=self.engine.prefill_chunk, prefilling=self.engine.num_prefilling)
+        if self.engine.fused_sampling:
+            st.update(fused_sampling=True)
         return st
 
     async def __call__(self, request):
         """HTTP: JSON body ``{"prompt_tokens": [...], "max_new_tokens": n}`` (optionally
-        ``temperature``, ``top_k``, ``eos_token_id``, ``seed``) -> newline-delimited token ids."""
+        ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``eos_token_id``, ``seed``) -> newline-delimited token ids."""
         body = json.loads(await request.body())
-        kw = {k: body[k] for k in ("max_new_tokens", "temperature", "top_k", "eos_token_id", "seed") if k in body}
+        kw = {k: body[k] for k in ("max_new_tokens", "temperature", "top_k", "top_p", "min_p", "eos_token_id", "seed")
+              if k in body}
 
         async def lines():
             async for tok in self.generate(body["prompt_tokens"], **kw):
