@@ -10,6 +10,11 @@ many prompt tokens (arrival order, one ``Llama.extend`` call) before the decode 
 prompt no longer stalls the running streams for its whole prefill. ``register_prefix`` keeps a
 prompt prefix in a pinned sequence whose whole pages later requests share (``PagedKVCache.fork``)
 instead of recomputing and storing them again.
+
+With ``speculative`` set (``models/speculative.py``), the decode phase of a step in which at least
+one live slot has a draft is one ``Llama.extend`` over the live slots' ``[last token] + draft``
+rows: every request emits the tokens the batched sampler would have drawn one step at a time, and
+the rejected drafts are rolled back out of the cache.
 """
 from __future__ import annotations
 
@@ -23,6 +28,7 @@ import torch
 from .. import ops
 from .kv_cache import PagedKVCache
 from .llama import _seeded_generator, sample_tokens, use_fused_sampling
+from .speculative import accept, draft_for, new_stats, resolve_speculative
 
 
 @dataclass
@@ -51,6 +57,8 @@ class _Request:
     min_p: float = 0.0
     seed: int = 0
     fused: bool = False
+    # shared prefix + prompt + produced tokens: what a speculative proposer drafts from
+    history: List[int] = field(default_factory=list)
 
 
 @dataclass
@@ -70,11 +78,17 @@ _NO_LIMIT = 1 << 62
 
 class GenerationEngine:
     def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8, num_blocks: int = 256,
-                 page_size: int = 16, prefill_chunk: Optional[int] = None, fused_sampling: bool = False):
+                 page_size: int = 16, prefill_chunk: Optional[int] = None, fused_sampling: bool = False,
+                 speculative=None):
+        """``speculative``: ``None``, a number of draft tokens per step (prompt lookup,
+        ``NgramProposer``) or a proposer object; it implies ``fused_sampling``, since a draft is
+        verified by re-drawing its token with ``ops.sample_logits``."""
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
-        self.fused_sampling = bool(fused_sampling)
+        self._proposer, self.num_draft = resolve_speculative(speculative)
+        self.fused_sampling = bool(fused_sampling) or self._proposer is not None
+        self.spec_stats = new_stats()
         self._prefixes = {}
         self.model = model
         w = model.embed.weight
@@ -164,8 +178,10 @@ class GenerationEngine:
             req.prefix = pfx
             pfx.users += 1
             req.feed = pfx.tokens[whole:] + prompt  # the partly filled page is recomputed per request
+            req.history = pfx.tokens + prompt
         else:
             req.feed = prompt
+            req.history = list(prompt)
         self.waiting.append(req)
         return rid
 
@@ -227,6 +243,7 @@ class GenerationEngine:
     def _emit(self, req: _Request, tok: int, events) -> bool:
         req.produced += 1
         req.last = tok
+        req.history.append(tok)
         finished = req.produced >= req.max_new_tokens or (req.eos_token_id is not None and tok == req.eos_token_id)
         events.append((req.rid, tok, finished))
         return finished
@@ -330,6 +347,11 @@ class GenerationEngine:
         """One decode step over the slots; requests still in their prompt, or that left it through
         ``extend`` in this step (``joined``), ride along as inactive slots."""
         live = [r is not None and not r.prefilling and r.rid not in joined for r in self.slots]
+        if any(live) and self._proposer is not None:
+            drafts = {slot: draft_for(self._proposer, self.num_draft, r.history, r.produced, r.max_new_tokens)
+                      for slot, r in enumerate(self.slots) if live[slot]}
+            if any(drafts.values()):
+                return self._verify(drafts, events)
         if any(live):
             seq_ids = [r.seq_id if on else None for r, on in zip(self.slots, live)]
             tokens = [r.last if on else 0 for r, on in zip(self.slots, live)]
@@ -338,6 +360,40 @@ class GenerationEngine:
             for (req, slot), tok in zip(picks, self._tokens(logits, picks)):
                 if self._emit(req, tok, events):
                     self._retire(slot)
+
+    def _verify(self, drafts, events):
+        """One verify step over the live slots (``drafts``: slot -> draft, possibly empty): feed
+        ``[last] + draft`` per slot through one ``extend``, draw every row's token with the row's
+        own parameters at step ``produced + j`` in one sampler call, emit the accepted prefix and
+        the token after it, and roll the rejected drafts back.
+
+        Admission arithmetic is untouched: ``draft_for`` caps a draft at ``max_new_tokens -
+        produced - 1`` tokens, so the cached length stays below prompt + ``max_new_tokens``, which
+        is what the request's blocks were reserved for; the extend cannot run out of blocks."""
+        slots = sorted(drafts)
+        reqs = [self.slots[s] for s in slots]
+        rows = [[r.last] + drafts[s] for s, r in zip(slots, reqs)]
+        logits = self.model.extend(rows, self.cache, [r.seq_id for r in reqs], all_logits=True, num_splits=None)
+        per_row = [(r, j) for r, row in zip(reqs, rows) for j in range(len(row))]
+        sampled = ops.sample_logits(logits, [r.temperature for r, _ in per_row], [r.top_k for r, _ in per_row],
+                                    [r.top_p for r, _ in per_row], [r.min_p for r, _ in per_row],
+                                    [r.seed for r, _ in per_row], [r.produced + j for r, j in per_row]).tolist()
+        self.spec_stats["verify_steps"] += 1
+        at = 0
+        for slot, req, row in zip(slots, reqs, rows):
+            draft = drafts[slot]
+            toks = accept(draft, sampled[at: at + len(row)], req.max_new_tokens - req.produced, req.eos_token_id)
+            at += len(row)
+            self.spec_stats["drafted"] += len(draft)
+            self.spec_stats["accepted"] += len(toks) - 1
+            self.spec_stats["emitted"] += len(toks)
+            finished = False
+            for tok in toks:  # consecutive events of one request; only the last can finish it
+                finished = self._emit(req, tok, events)
+            if finished:
+                self._retire(slot)
+            else:
+                self.cache.rollback(req.seq_id, len(draft) - (len(toks) - 1))  # the accepted drafts stay cached
 
     def step(self) -> List[Tuple[int, int, bool]]:
         """Admit, prefill, decode once, retire. Returns ``(request_id, token, finished)`` for every

@@ -312,9 +312,11 @@ class Llama(nn.Module):
         return self._cached_forward(tokens, cache, slots, (1, positions), attend)
 
     @torch.inference_mode()
-    def extend(self, tokens, cache, seq_ids):
+    def extend(self, tokens, cache, seq_ids, all_logits: bool = False, num_splits=1):
         """Append several new tokens to each sequence and return the logits ``[B, V]`` of each
-        sequence's last new token.
+        sequence's last new token, or with ``all_logits`` the logits ``[sum(len), V]`` of every fed
+        row in packed order (draft verification). ``num_splits`` goes to
+        ``ops.paged_attention_extend`` (``None``: its heuristic).
 
         ``tokens`` is a list of non-empty token lists; each ``seq_id`` may be new or already cached
         at any length (a prompt chunk, a further chat turn, draft tokens to verify). The batch is
@@ -347,15 +349,15 @@ class Llama(nn.Module):
 
         def attend(i, blk, qkv):
             return blk.attn.o(ops.paged_attention_extend(qkv, cache.k[i], cache.v[i], block_table, context_lens,
-                                                         cu_q_lens, max_q_len, Hq, Hk, D))
+                                                         cu_q_lens, max_q_len, Hq, Hk, D, num_splits=num_splits))
 
-        last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.long, device=dev)
+        last = None if all_logits else torch.tensor([c - 1 for c in cu[1:]], dtype=torch.long, device=dev)
         return self._cached_forward(flat, cache, slots, (1, positions), attend, last)
 
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
                  seed=None, cache=None, prefill_chunk=None, top_p: float = 1.0, min_p: float = 0.0,
-                 fused_sampling: bool = False):
+                 fused_sampling: bool = False, speculative=None):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
@@ -369,10 +371,18 @@ class Llama(nn.Module):
         ``ops.sample_logits`` call per step over all rows, every row seeded with ``seed`` (0 if
         ``None``) and stepped by the number of tokens produced so far, so a row's tokens are a
         function of ``seed`` and its own logits only. Without any of the three the
-        ``sample_tokens`` path runs, with the token streams it always gave."""
-        from .kv_cache import PagedKVCache
+        ``sample_tokens`` path runs, with the token streams it always gave.
 
-        fused = use_fused_sampling(fused_sampling, top_p, min_p)
+        ``speculative`` (``models/speculative.py``): ``None`` is the loop above; an ``int k`` drafts
+        up to ``k`` tokens per sequence and step by prompt lookup (``NgramProposer``), a proposer
+        object is used as given. The request then samples through ``ops.sample_logits`` as with
+        ``fused_sampling=True``, and its stream is that call's stream wherever ``extend`` and
+        ``decode_step`` agree on the logits; ``self.spec_stats`` holds the run's counts."""
+        from .kv_cache import PagedKVCache
+        from .speculative import resolve_speculative
+
+        proposer, num_draft = resolve_speculative(speculative)
+        fused = use_fused_sampling(fused_sampling or proposer is not None, top_p, min_p)
         if fused:
             ops.check_sampling_params([float(temperature)], [int(top_k)], [float(top_p)], [float(min_p)])
         if prefill_chunk is not None and int(prefill_chunk) < 1:
@@ -396,6 +406,10 @@ class Llama(nn.Module):
                 logits = self.prefill(prompts, None, cache, ids)
             else:
                 logits = self._chunked_prefill(prompts, cache, ids, int(prefill_chunk))
+            if proposer is not None:
+                return self._speculative_loop(prompts, ids, cache, logits, max_new_tokens, eos_token_id, proposer,
+                                              num_draft, (temperature, top_k, top_p, min_p,
+                                                          0 if seed is None else int(seed)))
             for step in range(max_new_tokens):
                 if fused:
                     nxt = ops.sample_logits(logits, temperature, top_k, top_p, min_p, 0 if seed is None else int(seed),
@@ -415,6 +429,57 @@ class Llama(nn.Module):
         finally:
             for sid in ids:
                 cache.free(sid)
+        return out
+
+    def _speculative_loop(self, prompts, ids, cache, logits, max_new_tokens, eos_token_id, proposer, num_draft, sampling):
+        """``generate``'s decode loop with drafts: per iteration one ``decode_step`` if no live
+        sequence has a draft, otherwise one ``extend`` over the live sequences' ``[last] + draft``
+        rows and one ``ops.sample_logits`` call over all of them, row ``j`` of a sequence at step
+        ``produced + j``. The caller frees the sequences."""
+        from .speculative import accept, draft_for, new_stats
+
+        temperature, top_k, top_p, min_p, seed = sampling
+        out = [[] for _ in prompts]
+        active = list(ids)
+        self.spec_stats = stats = new_stats()
+
+        def emit(b, toks):
+            out[b].extend(toks)
+            done = len(out[b]) >= max_new_tokens or (eos_token_id is not None and toks[-1] == eos_token_id)
+            if done:
+                cache.free(active[b])
+                active[b] = None
+            return done
+
+        first = ops.sample_logits(logits, temperature, top_k, top_p, min_p, seed, 0).tolist()
+        for b in range(len(prompts)):
+            emit(b, [first[b]])
+        while any(s is not None for s in active):
+            live = [b for b, s in enumerate(active) if s is not None]
+            drafts = {b: draft_for(proposer, num_draft, prompts[b] + out[b], len(out[b]), max_new_tokens) for b in live}
+            if not any(drafts.values()):
+                logits = self.decode_step([out[b][-1] if s is not None else 0 for b, s in enumerate(active)], cache,
+                                          active)
+                nxt = ops.sample_logits(logits, temperature, top_k, top_p, min_p, seed,
+                                        [len(o) for o in out]).tolist()
+                for b in live:
+                    emit(b, [nxt[b]])
+                continue
+            rows = [[out[b][-1]] + drafts[b] for b in live]
+            logits = self.extend(rows, cache, [active[b] for b in live], all_logits=True, num_splits=None)
+            steps = [len(out[b]) + j for b, r in zip(live, rows) for j in range(len(r))]
+            sampled = ops.sample_logits(logits, temperature, top_k, top_p, min_p, seed, steps).tolist()
+            stats["verify_steps"] += 1
+            at = 0
+            for b, r in zip(live, rows):
+                toks = accept(drafts[b], sampled[at: at + len(r)], max_new_tokens - len(out[b]), eos_token_id)
+                at += len(r)
+                stats["drafted"] += len(drafts[b])
+                stats["accepted"] += len(toks) - 1
+                stats["emitted"] += len(toks)
+                sid = active[b]
+                if not emit(b, toks):
+                    cache.rollback(sid, len(drafts[b]) - (len(toks) - 1))  # exactly the accepted drafts stay cached
         return out
 
     def _chunked_prefill(self, prompts, cache, ids, chunk):

@@ -40,6 +40,7 @@ __all__ = [
     "kv_cache_append_",
     "paged_attention_decode",
     "paged_attention_extend",
+    "paged_extend_num_splits",
     "sample_logits",
     "sample_logits_supported",
     "kernels_available",
@@ -1176,8 +1177,16 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
     return out
 
 
+def paged_extend_num_splits(B: int, Hk: int, max_q_len: int, G: int, max_context: int, page_size: int) -> int:
+    """The split count ``paged_attention_extend(num_splits=None)`` uses for ``B`` chunks of at most
+    ``max_q_len`` tokens, ``Hk`` kv heads of ``G`` query heads each and contexts of at most
+    ``max_context`` tokens (``rca_attn_extend_num_splits``); always in ``[1, 16]``."""
+    return int(lib().rca_attn_extend_num_splits(int(B), int(Hk), int(max_q_len), int(G),
+                                                min(int(max_context), 2 ** 31 - 1), int(page_size)))
+
+
 def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens, cu_q_lens, max_q_len: int, Hq: int,
-                           Hk: int, D: int, scale=None):
+                           Hk: int, D: int, scale=None, num_splits=1):
     """Causal attention of a ragged batch of query chunks over their paged KV caches, each chunk
     at the end of its sequence's context. Returns ``[T, Hq*D]``.
 
@@ -1189,9 +1198,16 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     n_b + i`` and attends keys ``0 .. position`` through ``block_table`` (int32 ``[B,
     max_blocks]``). Tokens past a context length never influence the result. ``max_q_len`` is an
     upper bound on the chunk lengths known on the host (it sizes the launch: no device
-    synchronisation here; longer chunks are cut to it); rows no sequence owns are undefined."""
+    synchronisation here; longer chunks are cut to it); rows no sequence owns are undefined.
+
+    ``num_splits`` splits every row tile's keys over that many workgroups, merged in a fixed order
+    (a few rows over a long context, such as draft tokens to verify, otherwise occupy a handful of
+    compute units). ``1`` (the default) is the unsplit launch; ``None`` asks
+    ``paged_extend_num_splits`` on ``max_blocks * page_size``. The reference path ignores it."""
     q = q_or_qkv
     B = _check_paged_attention("T", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D)
+    if num_splits is not None and int(num_splits) < 1:
+        raise ValueError("num_splits must be >= 1")
     T = q.shape[0]
     if cu_q_lens.dim() != 1:
         raise ValueError(f"cu_q_lens must be 1-D, got shape {tuple(cu_q_lens.shape)}")
@@ -1207,10 +1223,25 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     out = torch.empty(T, Hq * D, device=q.device, dtype=q.dtype)
     if T == 0 or B == 0 or max_q_len == 0:
         return out
-    check(lib().rca_attn_extend_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                      block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
-                                      out.data_ptr(), B, max_q_len, Hq, Hk, D, page, block_table.shape[1], num_blocks,
-                                      scale, stream_ptr(q.device)), "rca_attn_extend_paged")
+    max_blocks = block_table.shape[1]
+    if num_splits is None:
+        num_splits = paged_extend_num_splits(B, Hk, max_q_len, Hq // Hk, max_blocks * page, page)
+    num_splits = int(num_splits)
+    if num_splits == 1:
+        check(lib().rca_attn_extend_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                          block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
+                                          out.data_ptr(), B, max_q_len, Hq, Hk, D, page, max_blocks, num_blocks,
+                                          scale, stream_ptr(q.device)), "rca_attn_extend_paged")
+        return out
+    # transient, stream-ordered workspaces, as in paged_attention_decode
+    part_o = torch.empty(T, Hq, num_splits, D, device=q.device, dtype=torch.float32)
+    part_ml = torch.empty(T, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
+    check(lib().rca_attn_extend_paged_split(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                            block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
+                                            out.data_ptr(), part_o.data_ptr(), part_ml.data_ptr(), B, T, max_q_len, Hq,
+                                            Hk, D, page, max_blocks, num_blocks, scale, num_splits,
+                                            stream_ptr(q.device)), "rca_attn_extend_paged_split")
+    del part_o, part_ml
     return out
 
 

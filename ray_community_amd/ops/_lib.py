@@ -83,6 +83,9 @@ _SIGS = {
     "rca_attn_decode_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 7 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "rca_attn_decode_num_splits": (c_int, [c_int] * 4),
     "rca_attn_extend_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 6 + [c_int] * 8 + [c_float, c_void_p]),
+    "rca_attn_extend_paged_split": (c_int, [c_void_p, c_ll] + [c_void_p] * 8 + [c_int, c_ll] + [c_int] * 7
+                                    + [c_float, c_int, c_void_p]),
+    "rca_attn_extend_num_splits": (c_int, [c_int] * 6),
     "rca_sample_logits": (c_int, [c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
 

@@ -10,18 +10,18 @@
 // VALU in fp32 with a base-2 online softmax. Every (lane group, wave) keeps its own running
 // (m, l, O); they are merged by cross-lane butterflies, then across the 4 waves through LDS.
 // num_splits == 1 normalises and writes bf16 directly; otherwise fp32 partial O and (m, l) go to a
-// workspace that attn_decode_combine_kernel merges in split order (deterministic, no atomics).
+// workspace that attn_decode_combine_kernel (attention_combine.h) merges in split order
+// (deterministic, no atomics).
 //
 // Masking is by loop bounds and by not loading: a token at position >= context_lens[b] is never
 // read (its lanes get zero K/V and a -inf score), and block_table[b, j] is read only for
 // j < ceil(context_lens[b] / page_size), so NaN/Inf garbage in dead slots cannot reach the output.
+#include "attention_combine.h"
 #include "attention_common.h"
 
 namespace {
 
 constexpr int kDecWaves = 4;
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
 
 // exp2(a - m) with m == -inf (nothing seen yet) mapped to a zero reference: exp2(-inf - 0) = 0,
 // never exp2(-inf + inf) = NaN
@@ -228,43 +228,6 @@ __global__ __launch_bounds__(256, (G == 8 ? 1 : 2)) void attn_decode_paged_kerne
   }
 }
 
-// out[row] = sum_s exp2(m_s - m) O_s / sum_s exp2(m_s - m) l_s over the splits in index order.
-// Empty splits (m = -inf, l = 0) are skipped, not multiplied by zero; a row whose splits are all
-// empty (context_len 0) writes zeros. One thread per 8 output columns.
-__global__ __launch_bounds__(256) void attn_decode_combine_kernel(const float* __restrict__ part_o,
-                                                                  const float* __restrict__ part_ml,
-                                                                  bf16_t* __restrict__ out, long rows, int num_splits,
-                                                                  int D) {
-  const int lpt = D / 8;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  const long row = idx / lpt;
-  const int c = (int)(idx % lpt);
-  if (row >= rows) return;
-  const float* ml = part_ml + row * num_splits * 2;
-  float mt = neg_inf();
-  for (int s = 0; s < num_splits; ++s) mt = fmaxf(mt, ml[2 * s]);
-  float lt = 0.f, acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  for (int s = 0; s < num_splits; ++s) {
-    const float ms = ml[2 * s];
-    if (ms == neg_inf()) continue;
-    const float a = fast_exp2(ms - mt);
-    lt += a * ml[2 * s + 1];
-    const float* po = part_o + (row * num_splits + s) * D + c * 8;
-    const f32x4 x = *reinterpret_cast<const f32x4*>(po), y = *reinterpret_cast<const f32x4*>(po + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      acc[j] += a * x[j];
-      acc[4 + j] += a * y[j];
-    }
-  }
-  const float inv = lt > 0.f ? 1.f / lt : 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] *= inv;
-  *reinterpret_cast<u32x4*>(out + row * D + c * 8) = pack8(acc);
-}
-
 // One thread per 16-byte chunk of a token's K|V heads (qkv columns [Hq*D, (Hq+2Hk)*D)).
 __global__ __launch_bounds__(256) void kv_cache_append_kernel(const bf16_t* __restrict__ qkv, long row_stride,
                                                               const int* __restrict__ slot_mapping,
@@ -374,9 +337,6 @@ RCA_API int rca_attn_decode_paged(const void* q, long long q_stride, const void*
                              block_table, context_lens, max_blocks, num_blocks, page_size, B, Hk, scale_log2,
                              num_splits, (bf16_t*)out, (float*)part_o, (float*)part_ml, stream);
   if (rc != 0 || num_splits == 1) return rc;
-  const long rows = (long)B * Hq;
-  const long n = rows * (D / 8);
-  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                     (const float*)part_o, (const float*)part_ml, (bf16_t*)out, rows, num_splits, D);
-  return (int)hipGetLastError();
+  return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)B * Hq, num_splits, D,
+                              stream);
 }

@@ -39,21 +39,45 @@
 // j < 16) and c < D; the table index is < ceil(ctx / page_size) <= max_blocks because ctx is
 // clamped to max_blocks * page_size; q rows are cu_q_lens[b] + tok with tok < n_b <= max_q_len
 // (cu_q_lens itself is the caller's contract: non-decreasing, cu_q_lens[B] <= T).
+//
+// Split-KV (SPLIT = true; a few rows over a long context, e.g. draft tokens to verify): the grid's
+// x dimension is row tile * num_splits + split, and workgroup (row tile, split, hk, b) runs only
+// key tiles [split * tps, min((split + 1) * tps, ntile)) of its row tile, ntile being that row
+// tile's own causal bound and tps = ceil(ntile / num_splits). The range is a sub-range of
+// [0, ntile), and every rule above is stated per key tile (what is loaded, which table entry is
+// read, which scores are selected away), so each holds unchanged inside a split and the proof that
+// no global read leaves the buffers needs no new case: a split only visits fewer of the same
+// tiles. The first tile of the range is staged where the unsplit kernel stages tile 0, and the ring
+// buffer of a tile is its index relative to the range's start. Instead of the normalised bf16 row a
+// split stores, per (token, query head), the unnormalised fp32 O row and (m, l) into the decode
+// path's workspace layout (part_o fp32 [T, Hq, num_splits, D], part_ml fp32 [T, Hq, num_splits, 2]);
+// m is the base-2 scaled reference that O and l were accumulated against, which with the deferred
+// rescale may lie up to THR below the true maximum: the merge is exact for any consistent triple.
+// A split with no visible key for a row (an empty tile range, a row whose position lies before
+// the split's first key, a wave that skipped all its tiles) has m = -inf, l = 0 and stores only
+// that pair: attn_decode_combine_kernel (attention_combine.h) skips such a split without reading its
+// O row. Rows past n_b*G are not stored at all, as in the unsplit kernel. The workspace addresses
+// are the out address's (q0 + tok, hq) with the split index inside, so they stay inside
+// [T, Hq, num_splits, *] under the same cu_q_lens contract.
+#include "attention_combine.h"
 #include "attention_common.h"
 
 namespace {
 
-template <int D, int G>
+template <int D, int G, bool SPLIT>
 __global__ __launch_bounds__(kThreads, 2) void attn_extend_paged_kernel(
     const bf16_t* __restrict__ q, long q_stride, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const int* __restrict__ block_table, const int* __restrict__ context_lens, const int* __restrict__ cu_q_lens,
-    bf16_t* __restrict__ out, int max_q_len, int Hk, int page, int max_blocks, int num_blocks, float scale2) {
+    bf16_t* __restrict__ out, int max_q_len, int Hk, int page, int max_blocks, int num_blocks, float scale2,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int num_splits) {
   constexpr int BQ = 128, BK = 64, NKS = D / 16, NDB = D / 32, TILE = BK * D * 2, G8 = Img<D>::G8;
   constexpr int NCH = D / 8, N = BK * NCH / kThreads, RPI = kThreads / NCH;  // staging: Stage<D, BK>'s split
   constexpr float THR = 8.f;
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * TILE];
 
-  const int b = blockIdx.z, hk = blockIdx.y, r0 = blockIdx.x * BQ;
+  const int b = blockIdx.z, hk = blockIdx.y;
+  const int split = SPLIT ? (int)(blockIdx.x % (unsigned)num_splits) : 0;
+  const int r0 = (SPLIT ? (int)(blockIdx.x / (unsigned)num_splits) : (int)blockIdx.x) * BQ;
   const int q0 = cu_q_lens[b];
   int nq = cu_q_lens[b + 1] - q0;
   nq = nq < 0 ? 0 : (nq > max_q_len ? max_q_len : nq);
@@ -76,6 +100,10 @@ __global__ __launch_bounds__(kThreads, 2) void attn_extend_paged_kernel(
   const int pmax_w = prior + min(rw0 + 31, rows - 1) / G;
   const int kend = prior + min(r0 + BQ - 1, rows - 1) / G + 1;  // the tile's largest position + 1
   const int ntile = kend > 0 ? (kend + BK - 1) / BK : 0;
+  // this workgroup's key tiles [it0, it1): all of them, or its split's share (possibly none)
+  const int tps = SPLIT ? (ntile + num_splits - 1) / num_splits : ntile;
+  const int it0 = SPLIT ? min(split * tps, ntile) : 0;
+  const int it1 = SPLIT ? min(it0 + tps, ntile) : ntile;
 
   const int rb0 = Img<D>::row_base(l32, h, 0), rb1 = Img<D>::row_base(l32, h, 1);
   const int tb0 = Img<D>::tr_base(lane, 0), tb1 = Img<D>::tr_base(lane, 1);
@@ -149,8 +177,8 @@ __global__ __launch_bounds__(kThreads, 2) void attn_extend_paged_kernel(
     }
   };
 
-  if (ntile > 0) {
-    stage_load(0);
+  if (it0 < it1) {
+    stage_load(it0 * BK);
     dead_cur = dead_nxt;
     stage_store(smem);
   }
@@ -161,7 +189,7 @@ __global__ __launch_bounds__(kThreads, 2) void attn_extend_paged_kernel(
     const char* Ks = smem + buf * 2 * TILE;
     const char* Vs = Ks + TILE;
     const int kb = it * BK;
-    const bool more = it + 1 < ntile;
+    const bool more = it + 1 < it1;
     if (more) stage_load(kb + BK);
     if (w_live && kb <= pmax_w) {
       auto qk = [&](int t) {
@@ -244,13 +272,28 @@ __global__ __launch_bounds__(kThreads, 2) void attn_extend_paged_kernel(
     }
     __syncthreads();
   };
-  for (int it = 0; it < ntile; it += 2) {
+  for (int it = it0; it < it1; it += 2) {
     tile(IC<0>{}, it);
-    if (it + 1 < ntile) tile(IC<1>{}, it + 1);
+    if (it + 1 < it1) tile(IC<1>{}, it + 1);
   }
 
   const float lt = xhalf_sum(lsum);
   if (!valid) return;
+  if constexpr (SPLIT) {
+    // m is the same in both halves of a row (every rescale takes the cross-half maximum)
+    const long prow = ((long)(q0 + tok) * ((long)Hk * G) + hq) * num_splits + split;
+    if (h == 0) *reinterpret_cast<float2*>(part_ml + prow * 2) = float2{m, lt};  // nothing seen: (-inf, 0)
+    if (m == -INFINITY) return;  // the combine skips this split without reading its O row
+    float* Pr = part_o + prow * D;
+#pragma unroll
+    for (int db = 0; db < NDB; ++db) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<f32x4*>(Pr + 32 * db + 8 * g + 4 * h) =
+            f32x4{o[db][4 * g], o[db][4 * g + 1], o[db][4 * g + 2], o[db][4 * g + 3]};
+    }
+    return;
+  }
   const float inv = lt > 0.f ? 1.f / lt : 0.f;  // nothing visible (position < 0): zeros
   bf16_t* Or = out + (long)(q0 + tok) * ((long)Hk * G * D) + (long)hq * D;
 #pragma unroll
@@ -265,11 +308,12 @@ __global__ __launch_bounds__(kThreads, 2) void attn_extend_paged_kernel(
 
 // Explicit instantiations for every (D, G) the launcher selects (see attention.hip: hipcc has
 // dropped the host stub of a kernel template instantiated only through its launcher).
-#define RCA_EXT_INST(DD, GG)                                                                                        \
-  template __global__ void attn_extend_paged_kernel<DD, GG>(                                                        \
+#define RCA_EXT_INST1(DD, GG, SS)                                                                                   \
+  template __global__ void attn_extend_paged_kernel<DD, GG, SS>(                                                    \
       const bf16_t* __restrict__, long, const bf16_t* __restrict__, const bf16_t* __restrict__,                     \
       const int* __restrict__, const int* __restrict__, const int* __restrict__, bf16_t* __restrict__, int, int, int, \
-      int, int, float);
+      int, int, float, float* __restrict__, float* __restrict__, int);
+#define RCA_EXT_INST(DD, GG) RCA_EXT_INST1(DD, GG, false) RCA_EXT_INST1(DD, GG, true)
 RCA_EXT_INST(64, 1)
 RCA_EXT_INST(64, 2)
 RCA_EXT_INST(64, 4)
@@ -279,15 +323,18 @@ RCA_EXT_INST(128, 2)
 RCA_EXT_INST(128, 4)
 RCA_EXT_INST(128, 8)
 #undef RCA_EXT_INST
+#undef RCA_EXT_INST1
 
-template <int D>
+template <int D, bool SPLIT>
 int launch_extend_g(int G, dim3 grid, hipStream_t stream, const bf16_t* q, long q_stride, const bf16_t* kc,
                     const bf16_t* vc, const int* bt, const int* cl, const int* cu, bf16_t* out, int max_q_len, int Hk,
-                    int page, int max_blocks, int num_blocks, float scale2) {
-#define RCA_EXT(GG)                                                                                               \
-  case GG:                                                                                                        \
-    hipLaunchKernelGGL((attn_extend_paged_kernel<D, GG>), grid, dim3(kThreads), 0, stream, q, q_stride, kc, vc, bt, \
-                       cl, cu, out, max_q_len, Hk, page, max_blocks, num_blocks, scale2);                           \
+                    int page, int max_blocks, int num_blocks, float scale2, float* part_o, float* part_ml,
+                    int num_splits) {
+#define RCA_EXT(GG)                                                                                              \
+  case GG:                                                                                                       \
+    hipLaunchKernelGGL((attn_extend_paged_kernel<D, GG, SPLIT>), grid, dim3(kThreads), 0, stream, q, q_stride, kc, \
+                       vc, bt, cl, cu, out, max_q_len, Hk, page, max_blocks, num_blocks, scale2, part_o, part_ml,  \
+                       num_splits);                                                                              \
     return (int)hipGetLastError()
   switch (G) {
     RCA_EXT(1);
@@ -299,7 +346,59 @@ int launch_extend_g(int G, dim3 grid, hipStream_t stream, const bf16_t* q, long 
   return -1;
 }
 
+// The checks and the launch both entry points share. T (rows of q, out and the workspaces) is only
+// read when num_splits > 1.
+int extend_launch(const void* q, long long q_stride, const void* k_cache, const void* v_cache, const int* block_table,
+                  const int* context_lens, const int* cu_q_lens, void* out, void* part_o, void* part_ml, int B,
+                  long long T, int max_q_len, int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
+                  float scale, int num_splits, hipStream_t stream) {
+  if (B == 0 || max_q_len == 0) return 0;
+  if (B < 0 || max_q_len < 0 || Hq <= 0 || Hk <= 0 || Hq % Hk || (D != 64 && D != 128)) return -1;
+  if (page_size <= 0 || (page_size & 15) || max_blocks <= 0 || num_blocks <= 0 || !(scale > 0.f)) return -1;
+  if (q_stride < (long long)Hq * D || (q_stride & 7) || num_splits < 1 || (num_splits > 1 && T < 0)) return -1;
+  const int G = Hq / Hk;
+  const long long tiles = ((long long)max_q_len * G + 127) / 128 * num_splits;
+  if (B > 65535 || Hk > 65535 || tiles >= (1LL << 31) || (long long)num_blocks * page_size >= (1LL << 31)) return -2;
+  if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) return -3;
+  if (num_splits > 1 && (!part_o || !part_ml || (((uintptr_t)part_o | (uintptr_t)part_ml) & 15))) return -3;
+  const float scale2 = scale * 1.44269504088896340736f;
+  const dim3 grid((unsigned)tiles, Hk, B);
+#define RCA_EXT_ARGS                                                                                              \
+  G, grid, stream, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_table, \
+      context_lens, cu_q_lens, (bf16_t*)out, max_q_len, Hk, page_size, max_blocks, num_blocks, scale2,            \
+      (float*)part_o, (float*)part_ml, num_splits
+  if (num_splits == 1) return D == 128 ? launch_extend_g<128, false>(RCA_EXT_ARGS) : launch_extend_g<64, false>(RCA_EXT_ARGS);
+  const int rc = D == 128 ? launch_extend_g<128, true>(RCA_EXT_ARGS) : launch_extend_g<64, true>(RCA_EXT_ARGS);
+#undef RCA_EXT_ARGS
+  if (rc != 0 || T == 0) return rc;
+  return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)T * Hq, num_splits, D,
+                              stream);
+}
+
 }  // namespace
+
+// Default split count of the paged extend. The unsplit grid is row_tiles * Hk * B workgroups
+// (row_tiles = ceil(max_q_len * G / 128)), each walking its row tile's key tiles (64 keys) serially.
+// Heuristic:
+//   * aim for >= kExtWant workgroups;
+//   * a split walks at least kExtMinTiles key tiles (below that the partial-result write and the
+//     combine pass cost more than they spread);
+//   * at most 16 splits (the combine reads num_splits partials per output row);
+//   * 1 when the unsplit grid already reaches kExtWant workgroups (chunked prefill of a batch).
+// page_size takes no part: key tiles are 64 keys whatever the page. Measured values and the sweep
+// behind them: profiles/speculative_decoding.md.
+RCA_API int rca_attn_extend_num_splits(int B, int Hk, int max_q_len, int G, int max_context, int page_size) {
+  constexpr long kExtWant = 512, kExtMinTiles = 4;
+  (void)page_size;
+  if (B <= 0 || Hk <= 0 || max_q_len <= 0 || G <= 0 || max_context <= 0) return 1;
+  const long base = (((long)max_q_len * G + 127) / 128) * Hk * B;
+  const long want = (kExtWant + base - 1) / base;
+  const long by_work = (((long)max_context + 63) / 64) / kExtMinTiles;
+  long n = want < by_work ? want : by_work;
+  if (n > 16) n = 16;
+  if (n < 1) n = 1;
+  return (int)n;
+}
 
 // q: packed query rows, row t at q + t*q_stride (+ h*D per head; q_stride in elements: Hq*D for a
 // contiguous q, (Hq+2Hk)*D to read it in place from the fused qkv row). cu_q_lens: int32 [B+1],
@@ -310,21 +409,19 @@ RCA_API int rca_attn_extend_paged(const void* q, long long q_stride, const void*
                                   const int* block_table, const int* context_lens, const int* cu_q_lens, void* out,
                                   int B, int max_q_len, int Hq, int Hk, int D, int page_size, int max_blocks,
                                   int num_blocks, float scale, hipStream_t stream) {
-  if (B == 0 || max_q_len == 0) return 0;
-  if (B < 0 || max_q_len < 0 || Hq <= 0 || Hk <= 0 || Hq % Hk || (D != 64 && D != 128)) return -1;
-  if (page_size <= 0 || (page_size & 15) || max_blocks <= 0 || num_blocks <= 0 || !(scale > 0.f)) return -1;
-  if (q_stride < (long long)Hq * D || (q_stride & 7)) return -1;
-  const int G = Hq / Hk;
-  const long long tiles = ((long long)max_q_len * G + 127) / 128;
-  if (B > 65535 || Hk > 65535 || tiles >= (1LL << 31) || (long long)num_blocks * page_size >= (1LL << 31)) return -2;
-  if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) return -3;
-  const float scale2 = scale * 1.44269504088896340736f;
-  const dim3 grid((unsigned)tiles, Hk, B);
-  if (D == 128)
-    return launch_extend_g<128>(G, grid, stream, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache,
-                                (const bf16_t*)v_cache, block_table, context_lens, cu_q_lens, (bf16_t*)out, max_q_len,
-                                Hk, page_size, max_blocks, num_blocks, scale2);
-  return launch_extend_g<64>(G, grid, stream, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache,
-                             (const bf16_t*)v_cache, block_table, context_lens, cu_q_lens, (bf16_t*)out, max_q_len, Hk,
-                             page_size, max_blocks, num_blocks, scale2);
+  return extend_launch(q, q_stride, k_cache, v_cache, block_table, context_lens, cu_q_lens, out, nullptr, nullptr, B,
+                       0, max_q_len, Hq, Hk, D, page_size, max_blocks, num_blocks, scale, 1, stream);
+}
+
+// The same over num_splits splits of every row tile's keys, merged in split order (deterministic,
+// no atomics). T = rows of q and out; num_splits > 1 needs part_o (fp32 [T, Hq, num_splits, D]) and
+// part_ml (fp32 [T, Hq, num_splits, 2] = (m, l)), and then rows of out that no sequence owns are
+// written with whatever the workspace held. num_splits == 1 is rca_attn_extend_paged.
+RCA_API int rca_attn_extend_paged_split(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
+                                        const int* block_table, const int* context_lens, const int* cu_q_lens,
+                                        void* out, void* part_o, void* part_ml, int B, long long T, int max_q_len,
+                                        int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
+                                        float scale, int num_splits, hipStream_t stream) {
+  return extend_launch(q, q_stride, k_cache, v_cache, block_table, context_lens, cu_q_lens, out, part_o, part_ml, B, T,
+                       max_q_len, Hq, Hk, D, page_size, max_blocks, num_blocks, scale, num_splits, stream);
 }
