@@ -11,10 +11,12 @@ prompt no longer stalls the running streams for its whole prefill. ``register_pr
 prompt prefix in a pinned sequence whose whole pages later requests share (``PagedKVCache.fork``)
 instead of recomputing and storing them again.
 
-With ``speculative`` set (``models/speculative.py``), the decode phase of a step in which at least
-one live slot has a draft is one ``Llama.extend`` over the live slots' ``[last token] + draft``
-rows: every request emits the tokens the batched sampler would have drawn one step at a time, and
-the rejected drafts are rolled back out of the cache.
+The decode phase of a step is one ``decode_round`` (``models/decoding.py``, shared with
+``Llama.generate``) over the slots that are past their prompt. With ``speculative`` set
+(``models/speculative.py``), a round in which at least one live slot has a draft is one
+``Llama.extend`` over the live slots' ``[last token] + draft`` rows: every request emits the tokens
+the batched sampler would have drawn one step at a time, and the rejected drafts are rolled back
+out of the cache.
 """
 from __future__ import annotations
 
@@ -23,27 +25,16 @@ from collections import deque
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-import torch
-
-from .. import ops
+from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows
 from .kv_cache import PagedKVCache
-from .llama import _seeded_generator, sample_tokens, use_fused_sampling
-from .speculative import accept, draft_for, new_stats, resolve_speculative
+from .speculative import new_stats, resolve_speculative
 
 
-@dataclass
-class _Request:
+@dataclass(kw_only=True)
+class _Request(Stream):
+    """A ``Stream`` (``history`` starts as shared prefix + prompt) with its admission and prefill state."""
     rid: int
-    prompt: List[int]
-    max_new_tokens: int
-    temperature: float
-    top_k: int
-    eos_token_id: Optional[int]
-    generator: Optional[torch.Generator]
-    blocks: int                      # blocks the finished sequence will hold
-    produced: int = 0
-    last: int = 0                    # last emitted token (the next decode input)
-    seq_id: tuple = field(default=())
+    blocks: int                     # blocks the finished sequence will hold
     # chunked prefill / shared prefix (models.Llama.extend); unused on the plain prefill path
     feed: List[int] = field(default_factory=list)   # tokens to run through extend
     fed: int = 0                                    # ... of which this many are cached
@@ -51,14 +42,6 @@ class _Request:
     prefix: Optional["_Prefix"] = None              # held until the prefill is over
     forked: bool = False
     shared: int = 0                                 # blocks shared with the prefix (not in ``blocks``)
-    # batched sampler (ops.sample_logits): stepped by ``produced``, so the stream is a function of
-    # the seed and the request's own logits, never of its slot or its neighbours
-    top_p: float = 1.0
-    min_p: float = 0.0
-    seed: int = 0
-    fused: bool = False
-    # shared prefix + prompt + produced tokens: what a speculative proposer drafts from
-    history: List[int] = field(default_factory=list)
 
 
 @dataclass
@@ -97,7 +80,6 @@ class GenerationEngine:
         self.slots: List[Optional[_Request]] = [None] * int(max_slots)
         self.waiting = deque()
         self._ids = itertools.count()
-        self._sample = sample_tokens
 
     # -------------------------------------------------------------------------------- requests
     def register_prefix(self, tokens) -> int:
@@ -145,9 +127,7 @@ class GenerationEngine:
         ``top_p`` / ``min_p`` (``ops.sample_logits``) or the engine's ``fused_sampling`` put the
         request on the batched sampler: all such rows of a step's logits are sampled by one call,
         each with ``seed`` (0 if ``None``) and its own count of produced tokens as the step."""
-        fused = use_fused_sampling(self.fused_sampling, top_p, min_p)
-        ops.check_sampling_params([float(temperature)] if fused else [], [int(top_k)] if fused else [],
-                                  [float(top_p)], [float(min_p)])
+        sampling = Sampling(temperature, top_k, top_p, min_p, seed, self.fused_sampling)
         prompt = [int(t) for t in prompt]
         if not prompt or max_new_tokens < 1:
             raise ValueError("a request needs a non-empty prompt and max_new_tokens >= 1")
@@ -171,17 +151,14 @@ class GenerationEngine:
             raise ValueError(f"request needs {blocks} cache blocks, the cache has {self.cache.num_blocks}")
         gen = _seeded_generator(self.model.embed.weight.device, temperature, seed)
         rid = next(self._ids)
-        req = _Request(rid, prompt, int(max_new_tokens), float(temperature), int(top_k), eos_token_id, gen, blocks,
-                       seq_id=("engine", id(self), rid), top_p=float(top_p), min_p=float(min_p),
-                       seed=0 if seed is None else int(seed), fused=fused)
+        req = _Request(seq_id=("engine", id(self), rid), history=list(prompt), max_new_tokens=int(max_new_tokens),
+                       sampling=sampling, eos_token_id=eos_token_id, generator=gen, rid=rid, blocks=blocks,
+                       feed=prompt)
         if pfx is not None:
             req.prefix = pfx
             pfx.users += 1
             req.feed = pfx.tokens[whole:] + prompt  # the partly filled page is recomputed per request
             req.history = pfx.tokens + prompt
-        else:
-            req.feed = prompt
-            req.history = list(prompt)
         self.waiting.append(req)
         return rid
 
@@ -218,35 +195,13 @@ class GenerationEngine:
         return own + sum(p.blocks - self.cache.blocks_held(p.seq_id) for p in pfx.values())
 
     # ------------------------------------------------------------------------------------ step
-    def _tokens(self, logits, picks):
-        """The next token of every ``(request, row of logits)`` in ``picks``: the fused requests
-        through one ``ops.sample_logits`` call and one host copy, the others one by one."""
-        toks = [None] * len(picks)
-        fused = [n for n, (req, _) in enumerate(picks) if req.fused]
-        if fused:
-            rows = [picks[n][1] for n in fused]
-            reqs = [picks[n][0] for n in fused]
-            if rows != list(range(logits.shape[0])):
-                logits_f = logits[torch.tensor(rows, dtype=torch.long, device=logits.device)]
-            else:
-                logits_f = logits
-            out = ops.sample_logits(logits_f, [r.temperature for r in reqs], [r.top_k for r in reqs],
-                                    [r.top_p for r in reqs], [r.min_p for r in reqs], [r.seed for r in reqs],
-                                    [r.produced for r in reqs]).tolist()
-            for n, tok in zip(fused, out):
-                toks[n] = int(tok)
-        for n, (req, row) in enumerate(picks):
-            if not req.fused:
-                toks[n] = int(self._sample(logits[row][None], req.temperature, req.top_k, req.generator)[0])
-        return toks
-
-    def _emit(self, req: _Request, tok: int, events) -> bool:
-        req.produced += 1
-        req.last = tok
-        req.history.append(tok)
-        finished = req.produced >= req.max_new_tokens or (req.eos_token_id is not None and tok == req.eos_token_id)
-        events.append((req.rid, tok, finished))
-        return finished
+    def _emit(self, slot: int, toks, finished: bool, events):
+        """The events of one request's tokens of one round (only the last can finish it); a
+        finished request retires."""
+        rid = self.slots[slot].rid
+        events.extend((rid, tok, finished and n + 1 == len(toks)) for n, tok in enumerate(toks))
+        if finished:
+            self._retire(slot)
 
     def _retire(self, slot: int):
         req = self.slots[slot]
@@ -297,12 +252,12 @@ class GenerationEngine:
             obj.fed += len(toks)
             if slot is not None and obj.fed >= len(obj.feed):
                 emit.append((slot, obj, i))
-        for (slot, obj, _), tok in zip(emit, self._tokens(logits, [(obj, i) for _, obj, i in emit])):
+        for (slot, obj, _), tok in zip(emit, sample_rows(logits, [(obj, i) for _, obj, i in emit])):
             obj.prefilling = False
             self._unhold_prefix(obj)
-            if self._emit(obj, tok, events):
-                self._retire(slot)
-            else:
+            finished = obj.advance([tok])
+            self._emit(slot, [tok], finished, events)
+            if not finished:
                 done.add(obj.rid)
         return done
 
@@ -344,56 +299,12 @@ class GenerationEngine:
         return self._feed(self.model.extend, items, events) if items else set()
 
     def _decode(self, joined, events):
-        """One decode step over the slots; requests still in their prompt, or that left it through
+        """One decode round over the slots; requests still in their prompt, or that left it through
         ``extend`` in this step (``joined``), ride along as inactive slots."""
-        live = [r is not None and not r.prefilling and r.rid not in joined for r in self.slots]
-        if any(live) and self._proposer is not None:
-            drafts = {slot: draft_for(self._proposer, self.num_draft, r.history, r.produced, r.max_new_tokens)
-                      for slot, r in enumerate(self.slots) if live[slot]}
-            if any(drafts.values()):
-                return self._verify(drafts, events)
-        if any(live):
-            seq_ids = [r.seq_id if on else None for r, on in zip(self.slots, live)]
-            tokens = [r.last if on else 0 for r, on in zip(self.slots, live)]
-            logits = self.model.decode_step(tokens, self.cache, seq_ids)
-            picks = [(req, slot) for slot, req in enumerate(self.slots) if live[slot]]
-            for (req, slot), tok in zip(picks, self._tokens(logits, picks)):
-                if self._emit(req, tok, events):
-                    self._retire(slot)
-
-    def _verify(self, drafts, events):
-        """One verify step over the live slots (``drafts``: slot -> draft, possibly empty): feed
-        ``[last] + draft`` per slot through one ``extend``, draw every row's token with the row's
-        own parameters at step ``produced + j`` in one sampler call, emit the accepted prefix and
-        the token after it, and roll the rejected drafts back.
-
-        Admission arithmetic is untouched: ``draft_for`` caps a draft at ``max_new_tokens -
-        produced - 1`` tokens, so the cached length stays below prompt + ``max_new_tokens``, which
-        is what the request's blocks were reserved for; the extend cannot run out of blocks."""
-        slots = sorted(drafts)
-        reqs = [self.slots[s] for s in slots]
-        rows = [[r.last] + drafts[s] for s, r in zip(slots, reqs)]
-        logits = self.model.extend(rows, self.cache, [r.seq_id for r in reqs], all_logits=True, num_splits=None)
-        per_row = [(r, j) for r, row in zip(reqs, rows) for j in range(len(row))]
-        sampled = ops.sample_logits(logits, [r.temperature for r, _ in per_row], [r.top_k for r, _ in per_row],
-                                    [r.top_p for r, _ in per_row], [r.min_p for r, _ in per_row],
-                                    [r.seed for r, _ in per_row], [r.produced + j for r, j in per_row]).tolist()
-        self.spec_stats["verify_steps"] += 1
-        at = 0
-        for slot, req, row in zip(slots, reqs, rows):
-            draft = drafts[slot]
-            toks = accept(draft, sampled[at: at + len(row)], req.max_new_tokens - req.produced, req.eos_token_id)
-            at += len(row)
-            self.spec_stats["drafted"] += len(draft)
-            self.spec_stats["accepted"] += len(toks) - 1
-            self.spec_stats["emitted"] += len(toks)
-            finished = False
-            for tok in toks:  # consecutive events of one request; only the last can finish it
-                finished = self._emit(req, tok, events)
-            if finished:
-                self._retire(slot)
-            else:
-                self.cache.rollback(req.seq_id, len(draft) - (len(toks) - 1))  # the accepted drafts stay cached
+        live = [r if r is not None and not r.prefilling and r.rid not in joined else None for r in self.slots]
+        for slot, toks, finished in decode_round(self.model, self.cache, live, self._proposer, self.num_draft,
+                                                 self.spec_stats):
+            self._emit(slot, toks, finished, events)
 
     def step(self) -> List[Tuple[int, int, bool]]:
         """Admit, prefill, decode once, retire. Returns ``(request_id, token, finished)`` for every

@@ -378,13 +378,12 @@ class Llama(nn.Module):
         object is used as given. The request then samples through ``ops.sample_logits`` as with
         ``fused_sampling=True``, and its stream is that call's stream wherever ``extend`` and
         ``decode_step`` agree on the logits; ``self.spec_stats`` holds the run's counts."""
+        from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows, sample_tokens
         from .kv_cache import PagedKVCache
-        from .speculative import resolve_speculative
+        from .speculative import new_stats, resolve_speculative
 
         proposer, num_draft = resolve_speculative(speculative)
-        fused = use_fused_sampling(fused_sampling or proposer is not None, top_p, min_p)
-        if fused:
-            ops.check_sampling_params([float(temperature)], [int(top_k)], [float(top_p)], [float(min_p)])
+        sampling = Sampling(temperature, top_k, top_p, min_p, seed, fused_sampling or proposer is not None)
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         prompts = [list(p) for p in prompts]
@@ -397,90 +396,42 @@ class Llama(nn.Module):
             page = 16
             blocks = sum(-(-(len(p) + max_new_tokens) // page) for p in prompts)
             cache = PagedKVCache(self.cfg, blocks, page, device=dev, dtype=self.embed.weight.dtype)
-        gen = _seeded_generator(dev, temperature, seed)
+        sample = sample_rows
+        if not sampling.fused:
+            gen = _seeded_generator(dev, temperature, seed)
+
+            def sample(logits, picks):
+                # one batched draw on one generator over all rows, those of finished sequences
+                # included: the ``sample_tokens`` streams this path always gave
+                nxt = sample_tokens(logits, sampling.temperature, sampling.top_k, gen).tolist()
+                return [nxt[row] for _, row in picks]
+
         ids = [("generate", next(_SEQ_IDS)) for _ in prompts]
-        out = [[] for _ in prompts]
-        active = list(ids)
+        streams = [Stream(sid, list(p), max_new_tokens, sampling, eos_token_id) for sid, p in zip(ids, prompts)]
+        slots = list(streams)
+        stats = new_stats()
+        if proposer is not None:
+            self.spec_stats = stats
+
+        def settle(emitted):
+            for b, _, finished in emitted:
+                if finished:
+                    cache.free(ids[b])
+                    slots[b] = None
+
         try:
             if prefill_chunk is None:
                 logits = self.prefill(prompts, None, cache, ids)
             else:
                 logits = self._chunked_prefill(prompts, cache, ids, int(prefill_chunk))
-            if proposer is not None:
-                return self._speculative_loop(prompts, ids, cache, logits, max_new_tokens, eos_token_id, proposer,
-                                              num_draft, (temperature, top_k, top_p, min_p,
-                                                          0 if seed is None else int(seed)))
-            for step in range(max_new_tokens):
-                if fused:
-                    nxt = ops.sample_logits(logits, temperature, top_k, top_p, min_p, 0 if seed is None else int(seed),
-                                            step).tolist()
-                else:
-                    nxt = sample_tokens(logits, temperature, top_k, gen).tolist()
-                for b, sid in enumerate(active):
-                    if sid is None:
-                        continue
-                    out[b].append(nxt[b])
-                    if eos_token_id is not None and nxt[b] == eos_token_id:
-                        cache.free(sid)
-                        active[b] = None
-                if step + 1 == max_new_tokens or all(s is None for s in active):
-                    break
-                logits = self.decode_step([t if s is not None else 0 for t, s in zip(nxt, active)], cache, active)
+            first = sample(logits, [(st, b) for b, st in enumerate(streams)])
+            settle([(b, [tok], st.advance([tok])) for b, (st, tok) in enumerate(zip(streams, first))])
+            while any(st is not None for st in slots):
+                settle(decode_round(self, cache, slots, proposer, num_draft, stats, sample))
         finally:
             for sid in ids:
                 cache.free(sid)
-        return out
-
-    def _speculative_loop(self, prompts, ids, cache, logits, max_new_tokens, eos_token_id, proposer, num_draft, sampling):
-        """``generate``'s decode loop with drafts: per iteration one ``decode_step`` if no live
-        sequence has a draft, otherwise one ``extend`` over the live sequences' ``[last] + draft``
-        rows and one ``ops.sample_logits`` call over all of them, row ``j`` of a sequence at step
-        ``produced + j``. The caller frees the sequences."""
-        from .speculative import accept, draft_for, new_stats
-
-        temperature, top_k, top_p, min_p, seed = sampling
-        out = [[] for _ in prompts]
-        active = list(ids)
-        self.spec_stats = stats = new_stats()
-
-        def emit(b, toks):
-            out[b].extend(toks)
-            done = len(out[b]) >= max_new_tokens or (eos_token_id is not None and toks[-1] == eos_token_id)
-            if done:
-                cache.free(active[b])
-                active[b] = None
-            return done
-
-        first = ops.sample_logits(logits, temperature, top_k, top_p, min_p, seed, 0).tolist()
-        for b in range(len(prompts)):
-            emit(b, [first[b]])
-        while any(s is not None for s in active):
-            live = [b for b, s in enumerate(active) if s is not None]
-            drafts = {b: draft_for(proposer, num_draft, prompts[b] + out[b], len(out[b]), max_new_tokens) for b in live}
-            if not any(drafts.values()):
-                logits = self.decode_step([out[b][-1] if s is not None else 0 for b, s in enumerate(active)], cache,
-                                          active)
-                nxt = ops.sample_logits(logits, temperature, top_k, top_p, min_p, seed,
-                                        [len(o) for o in out]).tolist()
-                for b in live:
-                    emit(b, [nxt[b]])
-                continue
-            rows = [[out[b][-1]] + drafts[b] for b in live]
-            logits = self.extend(rows, cache, [active[b] for b in live], all_logits=True, num_splits=None)
-            steps = [len(out[b]) + j for b, r in zip(live, rows) for j in range(len(r))]
-            sampled = ops.sample_logits(logits, temperature, top_k, top_p, min_p, seed, steps).tolist()
-            stats["verify_steps"] += 1
-            at = 0
-            for b, r in zip(live, rows):
-                toks = accept(drafts[b], sampled[at: at + len(r)], max_new_tokens - len(out[b]), eos_token_id)
-                at += len(r)
-                stats["drafted"] += len(drafts[b])
-                stats["accepted"] += len(toks) - 1
-                stats["emitted"] += len(toks)
-                sid = active[b]
-                if not emit(b, toks):
-                    cache.rollback(sid, len(drafts[b]) - (len(toks) - 1))  # exactly the accepted drafts stay cached
-        return out
+        return [st.history[len(p):] for st, p in zip(streams, prompts)]
 
     def _chunked_prefill(self, prompts, cache, ids, chunk):
         """``prefill`` through ``extend``: ``chunk`` tokens per unfinished prompt per call."""
@@ -497,33 +448,8 @@ class Llama(nn.Module):
 _SEQ_IDS = itertools.count()
 
 
-def _seeded_generator(device, temperature, seed):
-    """The generator a request samples with: seeded (0 by default) on ``device``; ``None`` for
-    greedy decoding (``temperature == 0``)."""
-    if not temperature > 0:
-        return None
-    gen = torch.Generator(device=device)
-    gen.manual_seed(0 if seed is None else int(seed))
-    return gen
-
-
-def use_fused_sampling(fused_sampling, top_p, min_p) -> bool:
-    """Whether a request samples through ``ops.sample_logits``: on demand, or because it sets
-    ``top_p`` or ``min_p``, which only that sampler implements. Out-of-range values also go there,
-    to be refused by its checks."""
-    return bool(fused_sampling) or not float(top_p) == 1.0 or not float(min_p) == 0.0
-
-
-def sample_tokens(logits, temperature: float = 0.0, top_k: int = 0, generator=None):
-    """Next token per row of ``logits`` [B, V]: argmax at ``temperature == 0``, else a sample of
-    softmax(logits / temperature) restricted to the ``top_k`` largest logits (0: all)."""
-    if temperature <= 0:
-        return logits.argmax(dim=-1)
-    x = logits.float() / float(temperature)
-    if top_k and top_k < x.shape[-1]:
-        kth = x.topk(int(top_k), dim=-1).values[:, -1:]
-        x = x.masked_fill(x < kth, float("-inf"))
-    return torch.multinomial(torch.softmax(x, dim=-1), 1, generator=generator).reshape(-1)
+# sampling lives with the decode round; these names stay importable from here
+from .decoding import _seeded_generator, sample_tokens, use_fused_sampling  # noqa: E402,F401
 
 
 def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, **overrides) -> Llama:

@@ -8,6 +8,9 @@ speculative stream is therefore the plain ``fused_sampling`` stream, token for t
 for sampled requests, wherever ``extend`` and ``decode_step`` agree on the logits. For a
 deterministic proposer this rule is also the optimal one: P(accept) = p_target(draft).
 
+This module holds the host-side pieces (proposer, draft cap, acceptance rule, counters); the verify
+round itself is ``decoding.decode_round``, which ``Llama.generate`` and ``GenerationEngine`` share.
+
 A proposer is any object with ``propose(history: List[int], k: int) -> List[int]`` returning at
 most ``k`` tokens (possibly none); an optional ``num_draft`` attribute bounds ``k`` (default 4).
 """
