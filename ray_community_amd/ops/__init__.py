@@ -1037,7 +1037,9 @@ class _FlashAttn(torch.autograd.Function):
 
 def _token_major_ok(t):
     B, S, H, D = t.shape
-    return t.stride(3) == 1 and t.stride(2) == D and t.stride(0) == S * t.stride(1)
+    # the batch stride of a single batch element is never used (and torch leaves it arbitrary:
+    # x[:, :S] of a [1, S + 1, H, D] tensor is contiguous with stride(0) = (S + 1) * H * D)
+    return t.stride(3) == 1 and t.stride(2) == D and (B == 1 or t.stride(0) == S * t.stride(1))
 
 
 def flash_attention(q, k, v, causal: bool = True, scale=None):
