@@ -60,12 +60,24 @@ _NO_LIMIT = 1 << 62
 
 
 class GenerationEngine:
-    def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8, num_blocks: int = 256,
-                 page_size: int = 16, prefill_chunk: Optional[int] = None, fused_sampling: bool = False,
-                 speculative=None):
+    def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8,
+                 num_blocks: Optional[int] = None, page_size: int = 16, prefill_chunk: Optional[int] = None,
+                 fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
+                 cache_bytes: Optional[int] = None):
         """``speculative``: ``None``, a number of draft tokens per step (prompt lookup,
         ``NgramProposer``) or a proposer object; it implies ``fused_sampling``, since a draft is
-        verified by re-drawing its token with ``ops.sample_logits``."""
+        verified by re-drawing its token with ``ops.sample_logits``.
+
+        The engine's own cache has ``num_blocks`` blocks (default 256), or as many as fit into
+        ``cache_bytes`` (``PagedKVCache.block_bytes``; giving both is an error), of
+        ``kv_cache_dtype`` (``None`` / ``"auto"``: the model's dtype; ``"fp8"``: e4m3 pages with
+        per-token scales, ``(D + 4) / 2D`` of the bf16 bytes per block). Under fp8, ``prefill``
+        attends over the fresh, unquantised K/V while ``extend`` and ``decode_step`` read the
+        quantised cache, so a ``prefill_chunk`` stream may differ from the unchunked one;
+        speculative decoding keeps its guarantee, since the verify ``extend`` and ``decode_step``
+        read the same quantised bytes."""
+        if num_blocks is not None and cache_bytes is not None:
+            raise ValueError("give num_blocks or cache_bytes, not both")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
@@ -75,8 +87,14 @@ class GenerationEngine:
         self._prefixes = {}
         self.model = model
         w = model.embed.weight
-        self.cache = cache if cache is not None else PagedKVCache(model.cfg, num_blocks, page_size, device=w.device,
-                                                                  dtype=w.dtype)
+        if cache is None:
+            if cache_bytes is not None:
+                num_blocks = int(cache_bytes) // PagedKVCache.block_bytes(model.cfg, page_size, w.dtype, kv_cache_dtype)
+                if num_blocks < 1:
+                    raise ValueError(f"cache_bytes = {cache_bytes} holds no block of this model")
+            cache = PagedKVCache(model.cfg, 256 if num_blocks is None else num_blocks, page_size, device=w.device,
+                                 dtype=w.dtype, kv_dtype=kv_cache_dtype)
+        self.cache = cache
         self.slots: List[Optional[_Request]] = [None] * int(max_slots)
         self.waiting = deque()
         self._ids = itertools.count()

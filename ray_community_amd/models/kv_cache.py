@@ -19,23 +19,63 @@ class KVCacheFull(RuntimeError):
     """The paged KV cache has too few free blocks for the request (nothing was allocated)."""
 
 
+def _is_fp8(kv_dtype) -> bool:
+    """``kv_dtype`` as a flag: ``None`` / ``"auto"`` keep the model dtype, ``"fp8"`` /
+    ``torch.float8_e4m3fn`` select the quantised cache."""
+    if kv_dtype is None or kv_dtype == "auto":
+        return False
+    if kv_dtype == "fp8" or kv_dtype is torch.float8_e4m3fn:
+        return True
+    raise ValueError(f"kv_dtype must be None, 'auto', 'fp8' or torch.float8_e4m3fn, got {kv_dtype!r}")
+
+
 class PagedKVCache:
-    def __init__(self, cfg, num_blocks: int, page_size: int = 16, device=None, dtype=torch.bfloat16):
+    """``kv_dtype="fp8"`` stores K and V as ``float8_e4m3fn`` with one fp32 power-of-two scale per
+    (token, kv head): ``k_scale`` / ``v_scale`` are per-layer lists of ``[num_blocks, page_size,
+    Hk]`` tensors (``None`` for the unquantised cache). Scales live by slot, like the pages, so
+    ``fork`` shares them with the pages they belong to."""
+
+    def __init__(self, cfg, num_blocks: int, page_size: int = 16, device=None, dtype=torch.bfloat16, kv_dtype=None):
         if num_blocks <= 0 or page_size <= 0:
             raise ValueError("num_blocks and page_size must be positive")
         self.cfg = cfg
         self.num_blocks = int(num_blocks)
         self.page_size = int(page_size)
         self.device = torch.device(device if device is not None else "cpu")
-        self.dtype = dtype
+        self.fp8 = _is_fp8(kv_dtype)
+        self.dtype = torch.float8_e4m3fn if self.fp8 else dtype
         shape = (self.num_blocks, self.page_size, cfg.num_kv_heads, cfg.head_dim)
         # uninitialised on purpose: slots past a sequence's length are never read
-        self.k = [torch.empty(shape, device=self.device, dtype=dtype) for _ in range(cfg.num_layers)]
-        self.v = [torch.empty(shape, device=self.device, dtype=dtype) for _ in range(cfg.num_layers)]
+        self.k = [torch.empty(shape, device=self.device, dtype=self.dtype) for _ in range(cfg.num_layers)]
+        self.v = [torch.empty(shape, device=self.device, dtype=self.dtype) for _ in range(cfg.num_layers)]
+        self.k_scale = self.v_scale = None
+        if self.fp8:
+            self.k_scale = [torch.empty(shape[:3], device=self.device, dtype=torch.float32)
+                            for _ in range(cfg.num_layers)]
+            self.v_scale = [torch.empty(shape[:3], device=self.device, dtype=torch.float32)
+                            for _ in range(cfg.num_layers)]
         self._free: List[int] = list(range(self.num_blocks - 1, -1, -1))  # stack: block 0 goes first
         self._blocks: Dict[Hashable, List[int]] = {}
         self._lens: Dict[Hashable, int] = {}
         self._refs: List[int] = [0] * self.num_blocks  # owners per block (> 1 only after fork)
+
+    @staticmethod
+    def block_bytes(cfg, page_size: int, dtype=torch.bfloat16, kv_dtype=None) -> int:
+        """Bytes one block takes over all layers, K and V, the fp8 cache's scales included."""
+        rows = 2 * cfg.num_layers * int(page_size) * cfg.num_kv_heads  # head rows of a block
+        if _is_fp8(kv_dtype):
+            return rows * (cfg.head_dim + 4)
+        return rows * cfg.head_dim * torch.empty((), dtype=dtype).element_size()
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the cache's tensors."""
+        tensors = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in tensors)
+
+    def scales(self, layer: int):
+        """``(k_scale, v_scale)`` of a layer for the ``ops`` calls: ``(None, None)`` unless fp8."""
+        return (self.k_scale[layer], self.v_scale[layer]) if self.fp8 else (None, None)
 
     @property
     def num_free_blocks(self) -> int:

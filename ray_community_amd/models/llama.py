@@ -242,7 +242,8 @@ class Llama(nn.Module):
 
         def attn(i, blk, h):
             qkv = ops.apply_rope_(blk.attn.qkv(h), cs, seq_len, Hq, Hk, D, positions)
-            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D)
+            ks, vs = cache.scales(i)
+            ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D, k_scale=ks, v_scale=vs)
             return attend(i, blk, qkv)
 
         h = self._run_layers(self.embed(tokens), attn)
@@ -306,8 +307,9 @@ class Llama(nn.Module):
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
 
         def attend(i, blk, qkv):
+            ks, vs = cache.scales(i)
             return blk.attn.o(ops.paged_attention_decode(qkv, cache.k[i], cache.v[i], block_table, context_lens,
-                                                         Hq, Hk, D))
+                                                         Hq, Hk, D, k_scale=ks, v_scale=vs))
 
         return self._cached_forward(tokens, cache, slots, (1, positions), attend)
 
@@ -348,8 +350,10 @@ class Llama(nn.Module):
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
 
         def attend(i, blk, qkv):
+            ks, vs = cache.scales(i)
             return blk.attn.o(ops.paged_attention_extend(qkv, cache.k[i], cache.v[i], block_table, context_lens,
-                                                         cu_q_lens, max_q_len, Hq, Hk, D, num_splits=num_splits))
+                                                         cu_q_lens, max_q_len, Hq, Hk, D, num_splits=num_splits,
+                                                         k_scale=ks, v_scale=vs))
 
         last = None if all_logits else torch.tensor([c - 1 for c in cu[1:]], dtype=torch.long, device=dev)
         return self._cached_forward(flat, cache, slots, (1, positions), attend, last)
@@ -357,7 +361,7 @@ class Llama(nn.Module):
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
                  seed=None, cache=None, prefill_chunk=None, top_p: float = 1.0, min_p: float = 0.0,
-                 fused_sampling: bool = False, speculative=None):
+                 fused_sampling: bool = False, speculative=None, kv_cache_dtype=None):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
@@ -377,7 +381,13 @@ class Llama(nn.Module):
         up to ``k`` tokens per sequence and step by prompt lookup (``NgramProposer``), a proposer
         object is used as given. The request then samples through ``ops.sample_logits`` as with
         ``fused_sampling=True``, and its stream is that call's stream wherever ``extend`` and
-        ``decode_step`` agree on the logits; ``self.spec_stats`` holds the run's counts."""
+        ``decode_step`` agree on the logits; ``self.spec_stats`` holds the run's counts.
+
+        ``kv_cache_dtype`` (``None`` / ``"auto"`` / ``"fp8"``) is the dtype of the cache made here
+        (a ``cache`` passed in keeps its own). Under fp8, ``prefill`` attends over the fresh,
+        unquantised K/V while ``extend`` and ``decode_step`` read the quantised cache, so a
+        ``prefill_chunk`` stream may differ from the unchunked one. The speculative guarantee
+        holds: the verify ``extend`` and ``decode_step`` read the same quantised bytes."""
         from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows, sample_tokens
         from .kv_cache import PagedKVCache
         from .speculative import new_stats, resolve_speculative
@@ -395,7 +405,8 @@ class Llama(nn.Module):
         if cache is None:
             page = 16
             blocks = sum(-(-(len(p) + max_new_tokens) // page) for p in prompts)
-            cache = PagedKVCache(self.cfg, blocks, page, device=dev, dtype=self.embed.weight.dtype)
+            cache = PagedKVCache(self.cfg, blocks, page, device=dev, dtype=self.embed.weight.dtype,
+                                 kv_dtype=kv_cache_dtype)
         sample = sample_rows
         if not sampling.fused:
             gen = _seeded_generator(dev, temperature, seed)

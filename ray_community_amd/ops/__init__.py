@@ -37,6 +37,7 @@ __all__ = [
     "flash_attention_qkv",
     "flash_attention_supported",
     "paged_decode_supported",
+    "paged_kv_fp8_supported",
     "kv_cache_append_",
     "paged_attention_decode",
     "paged_attention_extend",
@@ -1060,7 +1061,13 @@ def paged_decode_supported(page_size: int, head_dim: int, n_q_heads: int, n_kv_h
             and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8))
 
 
-def _check_paged_caches(k_cache, v_cache, Hk, D):
+def paged_kv_fp8_supported(page_size: int, head_dim: int, n_q_heads: int, n_kv_heads: int) -> bool:
+    """Shapes the gfx950 fp8-cache kernels (quantising append, decode, extend) cover: the bf16
+    kernels' (others use the reference)."""
+    return paged_decode_supported(page_size, head_dim, n_q_heads, n_kv_heads)
+
+
+def _check_paged_caches(k_cache, v_cache, Hk, D, k_scale=None, v_scale=None):
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or tuple(k_cache.shape[2:]) != (Hk, D):
         raise ValueError(f"k_cache / v_cache must both be [num_blocks, page_size, {Hk}, {D}], got "
                          f"{tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
@@ -1068,6 +1075,31 @@ def _check_paged_caches(k_cache, v_cache, Hk, D):
         raise ValueError("k_cache and v_cache must share dtype and device")
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("k_cache and v_cache must be contiguous")
+    if k_scale is None and v_scale is None:
+        return
+    if k_scale is None or v_scale is None:
+        raise ValueError("k_scale and v_scale must be given together")
+    if k_cache.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"k_scale / v_scale go with float8_e4m3fn caches, got {k_cache.dtype}")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if tuple(t.shape) != tuple(k_cache.shape[:3]):
+            raise ValueError(f"{name} must be [num_blocks, page_size, Hk] = {tuple(k_cache.shape[:3])}, got "
+                             f"{tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+        if t.device != k_cache.device:
+            raise ValueError(f"{name} is on {t.device}, expected {k_cache.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+
+def _check_q_dtype(name, q, k_cache, fp8):
+    """``q`` / ``qkv`` against the caches: the same dtype, or any float dtype over an fp8 cache."""
+    if fp8:
+        if not q.dtype.is_floating_point or q.device != k_cache.device:
+            raise ValueError(f"{name} must be a float tensor on the caches' device")
+    elif q.dtype != k_cache.dtype or q.device != k_cache.device:
+        raise ValueError(f"{name} and the caches must share dtype and device")
 
 
 def _check_index(name, t, rows, device):
@@ -1082,19 +1114,24 @@ def _check_index(name, t, rows, device):
         raise ValueError(f"{name} must be contiguous")
 
 
-def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: int):
+def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: int, k_scale=None, v_scale=None):
     """Write the K and V heads of every token of the fused, already rotated ``qkv``
     ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]``, in place.
 
     ``slot_mapping`` (int32 ``[T]``) gives each token's slot ``block * page_size + offset``; ``-1``
     skips the token (padding). Slot values are not validated here (no device synchronisation):
-    they come from ``models.PagedKVCache``."""
-    _check_paged_caches(k_cache, v_cache, Hk, D)
+    they come from ``models.PagedKVCache``.
+
+    With ``k_scale`` / ``v_scale`` (fp32 ``[num_blocks, page_size, Hk]``) the caches are
+    ``float8_e4m3fn`` and every head row is quantised with its own power-of-two scale
+    (``reference.kv_quantize_fp8_ref``); ``qkv`` is bf16 on the kernel path, any float dtype on
+    the reference path."""
+    _check_paged_caches(k_cache, v_cache, Hk, D, k_scale, v_scale)
+    fp8 = k_scale is not None
     W = (Hq + 2 * Hk) * D
     if qkv.dim() != 2 or qkv.shape[1] != W or qkv.stride(1) != 1:
         raise ValueError(f"qkv must be [T, {W}] with unit inner stride, got {tuple(qkv.shape)}")
-    if qkv.dtype != k_cache.dtype or qkv.device != k_cache.device:
-        raise ValueError("qkv and the caches must share dtype and device")
+    _check_q_dtype("qkv", qkv, k_cache, fp8)
     T = qkv.shape[0]
     if slot_mapping.dim() != 1:
         raise ValueError(f"slot_mapping must be 1-D, got shape {tuple(slot_mapping.shape)}")
@@ -1102,23 +1139,29 @@ def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: i
     page = k_cache.shape[1]
     if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
             and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0):
+        if fp8:
+            check(lib().rca_kv_cache_append_fp8(qkv.data_ptr(), qkv.stride(0), slot_mapping.data_ptr(),
+                                                k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                                                v_scale.data_ptr(), T, Hq, Hk, D, k_cache.shape[0] * page,
+                                                stream_ptr(qkv.device)), "rca_kv_cache_append_fp8")
+            return
         check(lib().rca_kv_cache_append(qkv.data_ptr(), qkv.stride(0), slot_mapping.data_ptr(), k_cache.data_ptr(),
                                         v_cache.data_ptr(), T, Hq, Hk, D, k_cache.shape[0] * page,
                                         stream_ptr(qkv.device)), "rca_kv_cache_append")
         return
-    ref.kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D)
+    ref.kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D, k_scale, v_scale)
 
 
-def _check_paged_attention(letter, q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D):
+def _check_paged_attention(letter, q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, k_scale=None,
+                           v_scale=None):
     """The argument checks the paged attention ops share; returns the number of sequences ``B``.
     ``letter`` names q's rows: ``"B"`` (decode: one row per sequence, ``block_table`` checked
     first) or ``"T"`` (extend: ``context_lens`` says how many sequences, and is checked first)."""
-    _check_paged_caches(k_cache, v_cache, Hk, D)
+    _check_paged_caches(k_cache, v_cache, Hk, D, k_scale, v_scale)
     if q.dim() != 2 or q.shape[1] not in (Hq * D, (Hq + 2 * Hk) * D) or q.stride(1) != 1:
         raise ValueError(f"q must be [{letter}, {Hq * D}] or the fused [{letter}, {(Hq + 2 * Hk) * D}] row with unit "
                          f"inner stride, got {tuple(q.shape)}")
-    if q.dtype != k_cache.dtype or q.device != k_cache.device:
-        raise ValueError("q and the caches must share dtype and device")
+    _check_q_dtype("q", q, k_cache, k_scale is not None)
     B = q.shape[0] if letter == "B" else None
     for name in ("block_table", "context_lens") if letter == "B" else ("context_lens", "block_table"):
         t = block_table if name == "block_table" else context_lens
@@ -1140,7 +1183,7 @@ def _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D, *more) -> bool:
 
 
 def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens, Hq: int, Hk: int, D: int,
-                           scale=None, num_splits=None):
+                           scale=None, num_splits=None, k_scale=None, v_scale=None):
     """Single-token attention of ``B`` sequences over their paged KV caches. Returns ``[B, Hq*D]``.
 
     ``q_or_qkv`` is ``[B, Hq*D]`` or the fused ``[B, (Hq+2Hk)*D]`` row, whose q heads are read in
@@ -1148,15 +1191,20 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
     blocks in logical order; ``context_lens`` (int32 ``[B]``) its token count: tokens past it
     never influence the result (whatever bytes their slots hold), and a length of 0 gives a zero
     row. ``num_splits`` (default: ``rca_attn_decode_num_splits`` on ``max_blocks * page_size``)
-    splits each sequence's pages over that many workgroups, merged in a fixed order."""
+    splits each sequence's pages over that many workgroups, merged in a fixed order.
+
+    With ``k_scale`` / ``v_scale`` (fp32 ``[num_blocks, page_size, Hk]``) the caches are
+    ``float8_e4m3fn`` as ``kv_cache_append_`` wrote them; the result is the attention over the
+    dequantised cache (byte times scale, exact in bf16)."""
     q = q_or_qkv
-    B = _check_paged_attention("B", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D)
+    B = _check_paged_attention("B", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, k_scale, v_scale)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("num_splits must be >= 1")
     scale = float(D ** -0.5 if scale is None else scale)
     num_blocks, page = k_cache.shape[0], k_cache.shape[1]
     if not _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D):
-        return ref.paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale)
+        return ref.paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale,
+                                              k_scale, v_scale)
     out = torch.empty(B, Hq * D, device=q.device, dtype=q.dtype)
     if B == 0:
         return out
@@ -1171,6 +1219,14 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
         # work on this stream)
         part_o = torch.empty(B, Hq, num_splits, D, device=q.device, dtype=torch.float32)
         part_ml = torch.empty(B, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
+    if k_scale is not None:
+        check(L.rca_attn_decode_paged_fp8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                          k_scale.data_ptr(), v_scale.data_ptr(), block_table.data_ptr(),
+                                          context_lens.data_ptr(), out.data_ptr(), _p(part_o), _p(part_ml), B, Hq, Hk,
+                                          D, page, max_blocks, num_blocks, scale, num_splits, stream_ptr(q.device)),
+              "rca_attn_decode_paged_fp8")
+        del part_o, part_ml
+        return out
     check(L.rca_attn_decode_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                                   block_table.data_ptr(), context_lens.data_ptr(), out.data_ptr(), _p(part_o),
                                   _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale, num_splits,
@@ -1188,7 +1244,7 @@ def paged_extend_num_splits(B: int, Hk: int, max_q_len: int, G: int, max_context
 
 
 def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens, cu_q_lens, max_q_len: int, Hq: int,
-                           Hk: int, D: int, scale=None, num_splits=1):
+                           Hk: int, D: int, scale=None, num_splits=1, k_scale=None, v_scale=None):
     """Causal attention of a ragged batch of query chunks over their paged KV caches, each chunk
     at the end of its sequence's context. Returns ``[T, Hq*D]``.
 
@@ -1205,9 +1261,11 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     ``num_splits`` splits every row tile's keys over that many workgroups, merged in a fixed order
     (a few rows over a long context, such as draft tokens to verify, otherwise occupy a handful of
     compute units). ``1`` (the default) is the unsplit launch; ``None`` asks
-    ``paged_extend_num_splits`` on ``max_blocks * page_size``. The reference path ignores it."""
+    ``paged_extend_num_splits`` on ``max_blocks * page_size``. The reference path ignores it.
+
+    ``k_scale`` / ``v_scale``: the ``float8_e4m3fn`` cache, as in ``paged_attention_decode``."""
     q = q_or_qkv
-    B = _check_paged_attention("T", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D)
+    B = _check_paged_attention("T", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, k_scale, v_scale)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("num_splits must be >= 1")
     T = q.shape[0]
@@ -1221,7 +1279,7 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     num_blocks, page = k_cache.shape[0], k_cache.shape[1]
     if not _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D, num_blocks * page < 2 ** 31, scale > 0):
         return ref.paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, cu_q_lens, Hq, Hk, D,
-                                              scale)
+                                              scale, k_scale, v_scale)
     out = torch.empty(T, Hq * D, device=q.device, dtype=q.dtype)
     if T == 0 or B == 0 or max_q_len == 0:
         return out
@@ -1229,6 +1287,19 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     if num_splits is None:
         num_splits = paged_extend_num_splits(B, Hk, max_q_len, Hq // Hk, max_blocks * page, page)
     num_splits = int(num_splits)
+    if k_scale is not None:
+        part_o = part_ml = None
+        if num_splits > 1:
+            part_o = torch.empty(T, Hq, num_splits, D, device=q.device, dtype=torch.float32)
+            part_ml = torch.empty(T, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
+        check(lib().rca_attn_extend_paged_fp8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                              k_scale.data_ptr(), v_scale.data_ptr(), block_table.data_ptr(),
+                                              context_lens.data_ptr(), cu_q_lens.data_ptr(), out.data_ptr(),
+                                              _p(part_o), _p(part_ml), B, T, max_q_len, Hq, Hk, D, page, max_blocks,
+                                              num_blocks, scale, num_splits, stream_ptr(q.device)),
+              "rca_attn_extend_paged_fp8")
+        del part_o, part_ml
+        return out
     if num_splits == 1:
         check(lib().rca_attn_extend_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                                           block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),

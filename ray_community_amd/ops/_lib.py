@@ -82,6 +82,11 @@ _SIGS = {
                                     c_void_p]),
     "rca_attn_decode_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 7 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "rca_attn_decode_num_splits": (c_int, [c_int] * 4),
+    "rca_kv_cache_append_fp8": (c_int, [c_void_p, c_ll] + [c_void_p] * 5 + [c_ll, c_int, c_int, c_int, c_ll, c_void_p]),
+    "rca_attn_decode_paged_fp8": (c_int, [c_void_p, c_ll] + [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
+    "rca_attn_decode_fp8_set_step": (c_int, [c_int]),
+    "rca_attn_extend_paged_fp8": (c_int, [c_void_p, c_ll] + [c_void_p] * 10 + [c_int, c_ll] + [c_int] * 7
+                                  + [c_float, c_int, c_void_p]),
     "rca_attn_extend_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 6 + [c_int] * 8 + [c_float, c_void_p]),
     "rca_attn_extend_paged_split": (c_int, [c_void_p, c_ll] + [c_void_p] * 8 + [c_int, c_ll] + [c_int] * 7
                                     + [c_float, c_int, c_void_p]),

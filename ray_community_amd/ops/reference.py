@@ -160,24 +160,70 @@ def vtrace_ref(log_rhos, rewards, values, next_values, terminateds, dones, gamma
     return vs, pg
 
 
-def kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D):
+FP8_MAX = 448.0  # largest finite OCP e4m3 (torch.float8_e4m3fn) value
+
+
+def kv_quantize_fp8_ref(x):
+    """Quantise rows ``x[..., D]`` for the fp8 KV cache: returns ``(fp8 [..., D] float8_e4m3fn,
+    scale [...] float32)``. The scale of a row is the smallest power of two ``s`` with
+    ``max|x| / s <= 448``, clamped to ``[2^-126, 2^127]``, and 1 for an all-zero row; the stored
+    element is the round-to-nearest-even e4m3 of ``x / s`` (an exact fp32 quotient of at most 448,
+    so nothing saturates). Non-finite rows give unspecified values."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    mant, exp = torch.frexp(amax)  # amax = mant * 2^exp, mant in [0.5, 1); 448 = 0.875 * 2^9
+    k = exp - 9 + (mant > 0.875).to(exp.dtype)
+    k = torch.where(amax == 0, torch.zeros_like(k), k.clamp(-126, 127))
+    scale = ((k + 127).to(torch.int32) << 23).view(torch.float32)
+    return (xf / scale.unsqueeze(-1)).to(torch.float8_e4m3fn), scale
+
+
+def kv_dequantize_fp8_ref(fp8, scale, dtype=torch.bfloat16):
+    """``fp8 [..., D]`` times ``scale [...]`` in ``dtype``: exact in bf16 and fp32 (3 mantissa bits
+    times a power of two) wherever the product is a normal number of ``dtype``."""
+    return (fp8.float() * scale.unsqueeze(-1).float()).to(dtype)
+
+
+def kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D, k_scale=None, v_scale=None):
     """Copy the K and V heads of each token of the fused (already rotated) ``qkv``
     ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]`` at slot
-    ``slot_mapping[t]`` (= block * page_size + offset); ``-1`` skips the token. In place."""
+    ``slot_mapping[t]`` (= block * page_size + offset); ``-1`` skips the token. In place. With
+    ``k_scale`` / ``v_scale`` (``[num_blocks, page_size, Hk]`` fp32) the caches are fp8 and every
+    head row is quantised by ``kv_quantize_fp8_ref``."""
     T = qkv.shape[0]
     keep = slot_mapping >= 0
     slots = slot_mapping[keep].long()
     k = qkv[:, Hq * D: (Hq + Hk) * D].reshape(T, Hk, D)[keep]
     v = qkv[:, (Hq + Hk) * D: (Hq + 2 * Hk) * D].reshape(T, Hk, D)[keep]
+    if k_scale is not None:
+        k8, ks = kv_quantize_fp8_ref(k)
+        v8, vs = kv_quantize_fp8_ref(v)
+        # float8 tensors have no indexed assignment everywhere: write their bytes
+        k_cache.view(torch.uint8).view(-1, Hk, D)[slots] = k8.view(torch.uint8)
+        v_cache.view(torch.uint8).view(-1, Hk, D)[slots] = v8.view(torch.uint8)
+        k_scale.view(-1, Hk)[slots] = ks
+        v_scale.view(-1, Hk)[slots] = vs
+        return
     k_cache.view(-1, Hk, D)[slots] = k.to(k_cache.dtype)
     v_cache.view(-1, Hk, D)[slots] = v.to(v_cache.dtype)
 
 
-def paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale=None):
+def _dequantized_caches(q, k_cache, v_cache, k_scale, v_scale):
+    """The fp8 caches as exact caches of ``q``'s dtype (fp32 for other dtypes than bf16). Dead
+    slots may hold anything, NaN included: the callers never read them."""
+    dtype = torch.bfloat16 if q.dtype == torch.bfloat16 else torch.float32
+    return kv_dequantize_fp8_ref(k_cache, k_scale, dtype), kv_dequantize_fp8_ref(v_cache, v_scale, dtype)
+
+
+def paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale=None, k_scale=None,
+                               v_scale=None):
     """fp32 single-token attention over a paged cache: per sequence, gather its pages through
     ``block_table``, truncate to ``context_lens[b]`` tokens, softmax attention with GQA by head
     repetition. ``q`` is ``[B, >= Hq*D]`` (the q heads lead a fused qkv row). Returns
-    ``[B, Hq*D]`` in ``q``'s dtype; a sequence of length 0 gives zeros."""
+    ``[B, Hq*D]`` in ``q``'s dtype; a sequence of length 0 gives zeros. With ``k_scale`` /
+    ``v_scale`` the caches are fp8 and are dequantised first."""
+    if k_scale is not None:
+        k_cache, v_cache = _dequantized_caches(q, k_cache, v_cache, k_scale, v_scale)
     B = q.shape[0]
     page = k_cache.shape[1]
     scale = float(D ** -0.5 if scale is None else scale)
@@ -197,13 +243,17 @@ def paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, H
     return out.to(q.dtype)
 
 
-def paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, cu_q_lens, Hq, Hk, D, scale=None):
+def paged_attention_extend_ref(q, k_cache, v_cache, block_table, context_lens, cu_q_lens, Hq, Hk, D, scale=None,
+                               k_scale=None, v_scale=None):
     """fp32 causal attention of a ragged batch of query chunks over a paged cache. Sequence ``b``
     owns rows ``cu_q_lens[b] .. cu_q_lens[b+1]-1`` of ``q`` (``[T, >= Hq*D]``); ``context_lens[b]``
     counts its cached tokens including these ``n_b``, so query ``i`` sits at position
     ``context_lens[b] - n_b + i`` and attends keys ``0 .. position``, gathered through
     ``block_table``. Returns ``[T, Hq*D]`` in ``q``'s dtype; a sequence with ``n_b = 0``
-    contributes no rows, and rows no sequence owns are zero."""
+    contributes no rows, and rows no sequence owns are zero. With ``k_scale`` / ``v_scale`` the
+    caches are fp8 and are dequantised first."""
+    if k_scale is not None:
+        k_cache, v_cache = _dequantized_caches(q, k_cache, v_cache, k_scale, v_scale)
     T = q.shape[0]
     page = k_cache.shape[1]
     scale = float(D ** -0.5 if scale is None else scale)

@@ -20,8 +20,9 @@ from .api import deployment
 
 class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
-                 num_blocks: int = 256, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
-                 prefill_chunk=None, fused_sampling: bool = False, speculative=None):
+                 num_blocks=None, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
+                 prefill_chunk=None, fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
+                 cache_bytes=None):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
         ``torch.save``d state dict (without one the weights are initialised from ``seed``);
         ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
@@ -29,7 +30,10 @@ class _LlamaDeployment:
         ``fused_sampling``: every request samples through the engine's batched sampler
         (``ops.sample_logits``: one launch a step) instead of only those that set ``top_p`` / ``min_p``;
         ``speculative``: draft tokens per step by prompt lookup (or a proposer object), verified in
-        one forward (``GenerationEngine(speculative=...)``; implies ``fused_sampling``)."""
+        one forward (``GenerationEngine(speculative=...)``; implies ``fused_sampling``);
+        ``num_blocks`` (default 256) or ``cache_bytes`` size the KV cache and ``kv_cache_dtype``
+        (``"fp8"``: quantised pages, about half the bytes per token) picks its dtype, as in
+        ``GenerationEngine``."""
         import torch
 
         from ..models import GenerationEngine, build_llama
@@ -41,7 +45,8 @@ class _LlamaDeployment:
         self.model.eval()
         self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
                                        prefill_chunk=prefill_chunk, fused_sampling=fused_sampling,
-                                       speculative=speculative)
+                                       speculative=speculative, kv_cache_dtype=kv_cache_dtype,
+                                       cache_bytes=cache_bytes)
         self.default_max_new_tokens = int(default_max_new_tokens)
         # one model thread: the engine is not re-entrant, and per-thread GPU library state stays warm
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="llama-engine")
@@ -109,7 +114,8 @@ class _LlamaDeployment:
         [{"request_id", "max_new_tokens", "produced"}], "cancelled"}``; a deployment with
         ``prefill_chunk`` set adds ``"prefill_chunk"`` and ``"prefilling"`` (requests still in
         their prompt), one with ``fused_sampling`` adds ``"fused_sampling": True``, one with
-        ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``."""
+        ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``, one with an fp8
+        cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
                    for rid, e in list(self._queues.items())]
         st = {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
@@ -120,6 +126,9 @@ class _LlamaDeployment:
             st.update(fused_sampling=True)
         if self.engine.num_draft:
             st.update(speculative={"num_draft": self.engine.num_draft, **self.engine.spec_stats})
+        cache = self.engine.cache
+        if cache.fp8:
+            st.update(kv_cache_dtype="fp8", num_blocks=cache.num_blocks, cache_bytes=cache.nbytes)
         return st
 
     async def __call__(self, request):

@@ -11,6 +11,10 @@ that request's consecutive tokens and the newcomer's time to first token, for ``
 None, 512 and 2048.
 
     python scripts/extend_bench.py [--rounds 20] [--no-engine] [--json out.json]
+
+``--kv-dtype fp8`` measures the extend kernel over an FP8 KV cache against the bf16 cache instead,
+both arms interleaved in one process, at (B=4, prior 3584, chunk 512) and at a 5-row verify shape
+(B=8, prior 4091, split-KV by the default policy).
 """
 import argparse
 import json
@@ -84,6 +88,52 @@ def kernel_bench(rounds, iters, B, prior, chunk, Hq=32, Hk=8, D=128, page=16):
     return res
 
 
+def fp8_kernel_bench(rounds, iters, B, prior, chunk, Hq=32, Hk=8, D=128, page=16, num_splits=1):
+    """The extend kernel over a bf16 and over an fp8 cache holding the same K/V (N(0, 1), written
+    by the two append kernels), interleaved round by round in this process."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    ctx = prior + chunk
+    pages = -(-ctx // page)
+    num_blocks = B * pages
+    W = (Hq + 2 * Hk) * D
+    qkv = torch.randn(B * chunk, W, device=dev, dtype=torch.bfloat16, generator=g)
+    k_cache = torch.empty(num_blocks, page, Hk, D, device=dev, dtype=torch.bfloat16)
+    v_cache = torch.empty_like(k_cache)
+    k8 = torch.empty(num_blocks, page, Hk, D, device=dev, dtype=torch.float8_e4m3fn)
+    v8 = torch.empty_like(k8)
+    ks = torch.empty(num_blocks, page, Hk, device=dev, dtype=torch.float32)
+    vs = torch.empty_like(ks)
+    for s0 in range(0, num_blocks * page, 4096):
+        n = min(4096, num_blocks * page - s0)
+        rows = torch.randn(n, W, device=dev, dtype=torch.bfloat16, generator=g)
+        slots = torch.arange(s0, s0 + n, device=dev, dtype=torch.int32)
+        ops.kv_cache_append_(k_cache, v_cache, rows, slots, Hq, Hk, D)
+        ops.kv_cache_append_(k8, v8, rows, slots, Hq, Hk, D, k_scale=ks, v_scale=vs)
+    table = torch.randperm(num_blocks, device=dev, generator=g).to(torch.int32).view(B, pages)
+    lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    cu = torch.arange(0, (B + 1) * chunk, chunk, dtype=torch.int32, device=dev)
+    arms = {"bf16": lambda: ops.paged_attention_extend(qkv, k_cache, v_cache, table, lens, cu, chunk, Hq, Hk, D,
+                                                       num_splits=num_splits),
+            "fp8": lambda: ops.paged_attention_extend(qkv, k8, v8, table, lens, cu, chunk, Hq, Hk, D,
+                                                      num_splits=num_splits, k_scale=ks, v_scale=vs)}
+    times = {k: [] for k in arms}
+    for _ in range(2):  # warm-up
+        for fn in arms.values():
+            _time(fn, iters)
+    for _ in range(rounds):  # interleaved arms
+        for k, fn in arms.items():
+            times[k].append(_time(fn, iters))
+    flops = 4.0 * D * Hq * B * sum(range(prior + 1, ctx + 1))
+    splits = num_splits or ops.paged_extend_num_splits(B, Hk, chunk, Hq // Hk, pages * page, page)
+    res = {"shape": dict(B=B, prior=prior, chunk=chunk, Hq=Hq, Hk=Hk, D=D, page=page), "num_splits": splits}
+    for k, t in times.items():
+        us = statistics.median(t)
+        res[k] = {"us": round(us, 1), "us_min_max": [round(min(t), 1), round(max(t), 1)],
+                  "TFLOPs": round(flops / us / 1e6, 1)}
+    return res
+
+
 def engine_bench(model, prefill_chunk, prompt_len=4096, warm_tokens=8, reps=3):
     """Longest gap (ms) between consecutive tokens of a decoding request while a ``prompt_len``
     prompt arrives, and the newcomer's time to first token (ms). Median of ``reps``."""
@@ -127,9 +177,21 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--no-engine", action="store_true")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the extend kernel over an fp8 cache against the bf16 one, both arms in this process")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("extend_bench.py needs a GPU")
+    if args.kv_dtype == "fp8":
+        # a chunked-prefill shape, and 5 draft rows to verify over a long context (split-KV)
+        res = {"kernel": [fp8_kernel_bench(args.rounds, args.iters, 4, 3584, 512),
+                          fp8_kernel_bench(args.rounds, args.iters, 8, 4091, 5, num_splits=None)]}
+        for r in res["kernel"]:
+            print(json.dumps(r), flush=True)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     res = {"kernel": [kernel_bench(args.rounds, args.iters, 4, 3584, 512),
                       kernel_bench(args.rounds, args.iters, 1, 0, 4096)]}
     for r in res["kernel"]:
