@@ -28,6 +28,7 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(const bf16_t* __restrict__ 
 #pragma unroll
     for (int j = 1; j < 8; ++j) vm = fmaxf(vm, f[j]);
     const float mn = fmaxf(m, vm);
+    if (mn == -INFINITY) continue;  // only -inf (masked) logits so far: -inf - -inf would be NaN
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += __expf(f[j] - mn);
@@ -37,6 +38,7 @@ __global__ __launch_bounds__(512) void ce_fwd_kernel(const bf16_t* __restrict__ 
   for (int c = (nv << 3) + threadIdx.x; c < V; c += blockDim.x) {  // tail (V % 8)
     const float f = bf2f(x[c]);
     const float mn = fmaxf(m, f);
+    if (mn == -INFINITY) continue;
     s = s * __expf(m - mn) + __expf(f - mn);
     m = mn;
   }
@@ -148,11 +150,13 @@ __global__ __launch_bounds__(1024) void ce_fused_kernel(bf16_t* __restrict__ log
 #pragma unroll
       for (int j = 1; j < 8; ++j) vm = fmaxf(vm, f[j]);
       const float mn = fmaxf(m, vm);
-      float acc = 0.f;
+      if (mn != -INFINITY) {  // only -inf (masked) logits so far: -inf - -inf would be NaN
+        float acc = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc += __expf(f[j] - mn);
-      s = s * __expf(m - mn) + acc;
-      m = mn;
+        for (int j = 0; j < 8; ++j) acc += __expf(f[j] - mn);
+        s = s * __expf(m - mn) + acc;
+        m = mn;
+      }
     }
   }
 #pragma unroll
