@@ -921,18 +921,21 @@ extern "C" int rca_gemm4_bf16_internal(const GemmArgs* gp, int a_kmaj, int b_kma
 // dgu, dgu_t = SwiGLU-backward(gu, dh) with dh = dy W_down computed in registers (variant 7's
 // main loop, EPI 1): dy [T][H] (k = H contiguous, row stride ld_dy), w_t = W_down^T [F][H] (row
 // stride ld_w), gu / dgu [T][2F] contiguous, dgu_t [2F][T] contiguous.
-// Contract: T % 256 == 0, F % 256 == 0, H % 128 == 0, 16-B aligned rows; returns -1 otherwise.
+// Contract: T % 256 == 0, F % 256 == 0, H % 128 == 0, 16-B aligned rows; returns -1 otherwise, -2 for a
+// misaligned base pointer.
 // out[m][n] = act(sum_k x[m][k] w[n][k] + shift[n] (+ res[m][n])): a 1x1 NHWC convolution with the
 // folded-BatchNorm shift, residual add and ReLU in the epilogue (variant 7's main loop, EPI 2).
 // x [M][K] (row stride ldx), w [N][K] (ldw), out / res [M][N] (ldo / ldr), shift fp32 [N].
 // Contract: M % 256 == 0, N % 256 == 0, K % 128 == 0, 16-B aligned rows, each operand < 4 GB;
-// returns -1 otherwise.
+// returns -1 otherwise, -2 for a misaligned base pointer.
 RCA_API int rca_gemm_affine_act(const void* x, const void* w, const float* shift, const void* res, void* out, int M,
                                 int N, int K, long long ldx, long long ldw, long long ldo, long long ldr, int relu,
                                 hipStream_t st) {
   if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 128 || ldx % 8 || ldw % 8 || ldo % 4 ||
       (res && ldr % 4))
     return -1;
+  // 16-B LDS-DMA chunks and f32x4 shift loads, 8-B output / residual accesses
+  if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)shift) & 15) || (((uintptr_t)out | (uintptr_t)res) & 7)) return -2;
   if ((double)M * ldx * 2 >= 4294967296.0 || (double)N * ldw * 2 >= 4294967296.0) return -1;
   EpiArgs ep{};
   ep.shift = shift;
@@ -945,6 +948,8 @@ RCA_API int rca_gemm_affine_act(const void* x, const void* w, const float* shift
 RCA_API int rca_gemm_swiglu_bwd(const void* dy, const void* w_t, const void* gu, void* dgu, void* dgu_t, int T, int F,
                                 int H, long long ld_dy, long long ld_w, hipStream_t st) {
   if (T <= 0 || F <= 0 || H <= 0 || T % 256 || F % 256 || H % 128 || ld_dy % 8 || ld_w % 8) return -1;
+  // 16-B LDS-DMA chunks (dy, w_t) and transposed row stores (dgu_t), 8-B gu / dgu accesses
+  if ((((uintptr_t)dy | (uintptr_t)w_t | (uintptr_t)dgu_t) & 15) || (((uintptr_t)gu | (uintptr_t)dgu) & 7)) return -2;
   if ((double)T * ld_dy * 2 >= 4294967296.0 || (double)F * ld_w * 2 >= 4294967296.0) return -1;
   EpiArgs ep{(const bf16_t*)gu, (bf16_t*)dgu, (bf16_t*)dgu_t, 2L * F, 2L * F, (long)T, F};
   return launch4c<false, 24, 4, 96, 2, 1, 1, 1, 1>(GemmArgs{dy, w_t, nullptr, T, F, H, ld_dy, ld_w, 0, st}, ep);
