@@ -610,7 +610,10 @@ RCA_API int rca_adamw_split(void* hi16, void* lo16, const void* grad, int grad_d
 // Segmented launch (adamw_split_seg_kernel): segs = device int64 [nseg][8] as documented there,
 // nblocks = the last segment's first tile + its tile count (tiles are walked grid-stride by
 // min(nblocks, rca_adamw_split_set_blocks) workgroups). Contract: 16-B aligned buffers,
-// every segment offset a multiple of 8 elements, matrix R and C multiples of 64.
+// every segment offset a multiple of 8 elements, matrix R and C multiples of 128 (the kernel
+// tiles by 128: tilesC = C >> 7). The table lives in device memory, so R and C cannot be checked
+// here without a copy and a host sync: the Python caller enforces them (FlatAdamW._setup_transposed
+// gives a W^T pointer only to weights whose R and C are multiples of 128).
 RCA_API int rca_adamw_split_seg(void* hi16, void* lo16, const void* grad, int grad_dtype, float* m, float* v,
                                 const void* segs, int nseg, long long nblocks, float lr, float b1, float b2, float eps,
                                 float wd, float bc1, float bc2, float grad_mul, const float* sumsq, float max_norm,

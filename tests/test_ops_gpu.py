@@ -773,7 +773,7 @@ def test_adamw_split_master_kernel_matches_fp32_master(gdt, n):
 
 @pytest.mark.parametrize("gdt", [torch.bfloat16, torch.float32])
 def test_adamw_segmented_with_transposed_weights_bitwise(gdt):
-    """The segmented split-master AdamW (rca_adamw_split_seg: 64x64 matrix tiles that also write
+    """The segmented split-master AdamW (rca_adamw_split_seg: 128x128 matrix tiles that also write
     W^T, 1-D blocks for everything else) is bit-identical to the flat kernel on weights, low
     halves, m and v, across decay / no-decay params and odd-length tails; every fused-wgrad
     weight's W^T equals W.t() exactly after each step and the backward's weight_t() uses it."""
