@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..parallel.fused_linear import FusedEmbedding, FusedWgradLinear, swiglu_down
+from .quant import QuantLinear, quantize_weights_
 
 
 @dataclass
@@ -126,6 +127,8 @@ class MLP(nn.Module):
         # On the flat-gradient GPU path SwiGLU also writes act^T (the down projection's wgrad
         # operand), and the backward's down dgrad GEMM applies the SwiGLU backward in its epilogue,
         # writing d(gate|up) and its transpose for the gate_up wgrad (parallel/fused_linear.py).
+        if isinstance(self.down, QuantLinear):  # fp8 weights (inference only): the two separate ops
+            return self.down(ops.swiglu(self.gate_up(x)))
         return swiglu_down(self.gate_up(x), self.down)
 
 
@@ -162,6 +165,12 @@ class Llama(nn.Module):
                 p.normal_(0.0, out_std)
             else:
                 p.normal_(0.0, std)
+
+    def quantize_weights_(self, dtype="fp8"):
+        """Quantise the linears' weights in place for inference (``models/quant.py``): ``"fp8"``
+        halves their bytes; ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run
+        ``ops.linear_w8``. Idempotent. Training paths are not available afterwards."""
+        return quantize_weights_(self, dtype)
 
     def rope_table(self, device):
         key = str(device)
@@ -463,7 +472,9 @@ _SEQ_IDS = itertools.count()
 from .decoding import _seeded_generator, sample_tokens, use_fused_sampling  # noqa: E402,F401
 
 
-def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, **overrides) -> Llama:
+def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, weight_dtype=None, **overrides) -> Llama:
+    """``weight_dtype``: ``None`` / ``"auto"`` keep the linears in ``dtype``; ``"fp8"`` quantises them
+    (``Llama.quantize_weights_``) after the cast."""
     cfg = PRESETS[name_or_cfg] if isinstance(name_or_cfg, str) else name_or_cfg
     if overrides:
         cfg = LlamaConfig(**{**cfg.__dict__, **overrides})
@@ -472,4 +483,4 @@ def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, **ov
             m = Llama(cfg)
     else:
         m = Llama(cfg)
-    return m.to(dtype=dtype)
+    return m.to(dtype=dtype).quantize_weights_(weight_dtype)

@@ -44,6 +44,9 @@ __all__ = [
     "paged_extend_num_splits",
     "sample_logits",
     "sample_logits_supported",
+    "linear_w8",
+    "linear_w8_supported",
+    "dequant_w8",
     "kernels_available",
 ]
 
@@ -1429,3 +1432,102 @@ def sample_logits(logits, temperature, top_k=0, top_p=1.0, min_p=0.0, seeds=0, s
                                   params.data_ptr(), _p(uniforms), out.data_ptr(), B, V, stream_ptr(logits.device)),
           "rca_sample_logits")
     return out
+
+
+# ----------------------------------------------------------------------------------- FP8 weights
+# Rows up to which ``linear_w8`` runs the W8A16 kernel (ops/csrc/linear_w8.hip); above it the weight is
+# dequantised into a workspace and the product is a bf16 ``F.linear``. 32 is the kernel's single-pass
+# row tile (one stream of the weight) and the largest measured M at which the kernel beats the bf16 arm
+# on every llama3-8b shape (at M = 64 it loses on gate_up and lm_head): profiles/weight_fp8.md.
+M_SKINNY = 32
+
+
+def _w8_tensor_ok(t) -> bool:
+    if not (torch.is_tensor(t) and t.is_cuda and t.data_ptr() % 16 == 0):
+        return False
+    if t.dtype == torch.bfloat16:  # x / out: row-strided views
+        return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1]
+    if t.dtype in (torch.float8_e4m3fn, torch.uint8):  # the weight's e4m3 bytes
+        return t.dim() == 2 and t.is_contiguous()
+    return t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()  # the scales
+
+
+def linear_w8_supported(M: int, N: int, K: int, *tensors) -> bool:
+    """What the W8A16 kernel takes: ``K % 128 == 0``, ``N % 16 == 0``, ``M >= 1``; CUDA tensors with
+    16-byte aligned bases: bf16 2-D ``x`` / ``out`` with unit inner stride and a row stride that is
+    a multiple of 8, a contiguous e4m3 (or uint8) ``[N, K]`` weight, contiguous fp32 scales."""
+    return M >= 1 and N > 0 and K > 0 and N % 16 == 0 and K % 128 == 0 and all(_w8_tensor_ok(t) for t in tensors)
+
+
+def _linear_w8_kernel(x2, qweight, scale, out):
+    """The kernel launch on operands ``linear_w8_supported`` accepts, whatever M is."""
+    M, K = x2.shape
+    N = qweight.shape[0]
+    L = lib()
+    splits = L.rca_linear_w8_splits(N, K)
+    ws = _workspace(x2.device, "linear_w8_split", splits * M * N) if splits > 1 else None
+    check(L.rca_linear_w8a16(x2.data_ptr(), qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), _p(ws),
+                             ws.numel() * 4 if ws is not None else 0, M, N, K, x2.stride(0), out.stride(0),
+                             stream_ptr(x2.device)), "linear_w8a16")
+    return out
+
+
+def dequant_w8(qweight, scale, out=None):
+    """``qweight [N, K]`` (e4m3 bytes) times ``scale [N]`` as bf16 ``[N, K]``: exact. GPU: one
+    vectorised kernel; CPU: ``reference.kv_dequantize_fp8_ref``."""
+    if qweight.dtype == torch.uint8:
+        qweight = qweight.view(torch.float8_e4m3fn)
+    N, K = qweight.shape
+    if not (K % 16 == 0 and _w8_tensor_ok(qweight) and _w8_tensor_ok(scale) and scale.shape[0] == N):
+        w = ref.kv_dequantize_fp8_ref(qweight, scale)
+        return w if out is None else out.copy_(w)
+    if out is None:
+        out = torch.empty((N, K), device=qweight.device, dtype=torch.bfloat16)
+    elif not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (N, K)
+              and out.data_ptr() % 16 == 0):
+        raise ValueError("dequant_w8: out must be a contiguous, 16-byte aligned bf16 [N, K] CUDA tensor")
+    check(lib().rca_dequant_w8(qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), N, K, stream_ptr(out.device)),
+          "dequant_w8")
+    return out
+
+
+def linear_w8(x, qweight, scale, out=None):
+    """``x [..., K] @ (qweight [N, K] * scale [N]).T`` for an fp8-quantised weight
+    (``reference.quantize_weight_fp8_ref``: e4m3 bytes, held as ``float8_e4m3fn`` or ``uint8``, and
+    one power-of-two fp32 scale per output row). No autograd: inference only.
+
+    bf16 CUDA ``x`` within ``linear_w8_supported``: up to ``M_SKINNY`` rows run the W8A16 kernel
+    (the weight is streamed as bytes, converted to bf16 in registers, accumulated in fp32 on the
+    MFMA, scaled and rounded once; an output row depends on its own input row only, not on the batch
+    it came in). More rows (prefill) dequantise the weight into one per-device bf16 workspace on
+    the current stream and call ``F.linear``. An ``x`` with a non-unit inner stride or a misaligned
+    base is made contiguous first. CPU tensors, other dtypes and shapes outside the contract run
+    ``reference.linear_w8_ref``. ``out``: a bf16 ``[M, N]`` tensor or view to write."""
+    if qweight.dtype == torch.uint8:
+        qweight = qweight.view(torch.float8_e4m3fn)
+    N, K = qweight.shape
+    if x.shape[-1] != K or scale.shape != (N,):
+        raise ValueError(f"linear_w8: x [..., {x.shape[-1]}], qweight [{N}, {K}] and scale {tuple(scale.shape)} "
+                         "do not agree")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if out is not None and (tuple(out.shape) != (M, N) or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError(f"linear_w8: out must be a {x.dtype} [{M}, {N}] tensor on {x.device}")
+    if x2.is_cuda and x2.dtype == torch.bfloat16 and not _w8_tensor_ok(x2):
+        x2 = x2.contiguous()
+    if not linear_w8_supported(M, N, K, x2, qweight, scale):
+        y = ref.linear_w8_ref(x2, qweight, scale)
+    elif M <= M_SKINNY:
+        direct = out is not None and _w8_tensor_ok(out)
+        y = _linear_w8_kernel(x2, qweight, scale,
+                              out if direct else torch.empty((M, N), device=x.device, dtype=torch.bfloat16))
+        if direct:
+            return out
+    else:
+        w = dequant_w8(qweight, scale, _workspace(x.device, "linear_w8_dequant", N * K, torch.bfloat16)[:N * K].view(N, K))
+        y = torch.nn.functional.linear(x2, w)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y.view(*lead, N)

@@ -184,6 +184,23 @@ def kv_dequantize_fp8_ref(fp8, scale, dtype=torch.bfloat16):
     return (fp8.float() * scale.unsqueeze(-1).float()).to(dtype)
 
 
+def quantize_weight_fp8_ref(w):
+    """Quantise a linear's weight ``[N, K]`` to fp8, one power-of-two scale per output row:
+    ``kv_quantize_fp8_ref`` on the rows of ``w`` (a zero row gets scale 1). Returns ``(q [N, K]
+    float8_e4m3fn, s [N] float32)``; ``kv_dequantize_fp8_ref(q, s)`` is exact in bf16 and fp32."""
+    if w.dim() != 2:
+        raise ValueError("quantize_weight_fp8_ref: weight must be [N, K]")
+    return kv_quantize_fp8_ref(w)
+
+
+def linear_w8_ref(x, qweight, scale):
+    """``x [..., K] @ (qweight [N, K] * scale [N]).T`` with the weight dequantised (exactly) to
+    ``x.dtype``: the reference of ``ops.linear_w8``."""
+    if qweight.dtype == torch.uint8:
+        qweight = qweight.view(torch.float8_e4m3fn)
+    return torch.nn.functional.linear(x, kv_dequantize_fp8_ref(qweight, scale, x.dtype))
+
+
 def kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D, k_scale=None, v_scale=None):
     """Copy the K and V heads of each token of the fused (already rotated) ``qkv``
     ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]`` at slot

@@ -22,7 +22,7 @@ class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
                  num_blocks=None, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
                  prefill_chunk=None, fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
-                 cache_bytes=None):
+                 cache_bytes=None, weight_dtype=None):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
         ``torch.save``d state dict (without one the weights are initialised from ``seed``);
         ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
@@ -33,16 +33,21 @@ class _LlamaDeployment:
         one forward (``GenerationEngine(speculative=...)``; implies ``fused_sampling``);
         ``num_blocks`` (default 256) or ``cache_bytes`` size the KV cache and ``kv_cache_dtype``
         (``"fp8"``: quantised pages, about half the bytes per token) picks its dtype, as in
-        ``GenerationEngine``."""
+        ``GenerationEngine``; ``weight_dtype`` (``None`` / ``"auto"`` / ``"fp8"``): ``"fp8"`` quantises
+        the linears' weights once the state dict is loaded (``Llama.quantize_weights_``: half the
+        weight bytes, activations stay in ``dtype``)."""
         import torch
 
-        from ..models import GenerationEngine, build_llama
+        from ..models import GenerationEngine, build_llama, weight_bytes
 
         torch.manual_seed(seed)
         self.model = build_llama(model, device=device, dtype=getattr(torch, dtype) if isinstance(dtype, str) else dtype)
         if state_dict_path is not None:
             self.model.load_state_dict(torch.load(state_dict_path, map_location=device))
+        self.model.quantize_weights_(weight_dtype)
         self.model.eval()
+        self.weight_dtype = "fp8" if weight_dtype == "fp8" else None
+        self.weight_bytes = weight_bytes(self.model)
         self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
                                        prefill_chunk=prefill_chunk, fused_sampling=fused_sampling,
                                        speculative=speculative, kv_cache_dtype=kv_cache_dtype,
@@ -115,7 +120,8 @@ class _LlamaDeployment:
         ``prefill_chunk`` set adds ``"prefill_chunk"`` and ``"prefilling"`` (requests still in
         their prompt), one with ``fused_sampling`` adds ``"fused_sampling": True``, one with
         ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``, one with an fp8
-        cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``."""
+        cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``, one with fp8
+        weights adds ``"weight_dtype": "fp8"`` and ``"weight_bytes"`` (the model's parameters and buffers)."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
                    for rid, e in list(self._queues.items())]
         st = {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
@@ -129,6 +135,8 @@ class _LlamaDeployment:
         cache = self.engine.cache
         if cache.fp8:
             st.update(kv_cache_dtype="fp8", num_blocks=cache.num_blocks, cache_bytes=cache.nbytes)
+        if self.weight_dtype is not None:
+            st.update(weight_dtype=self.weight_dtype, weight_bytes=self.weight_bytes)
         return st
 
     async def __call__(self, request):
