@@ -78,6 +78,7 @@ class Stream:
     eos_token_id: Optional[int] = None
     generator: Optional[torch.Generator] = None   # of the ``sample_tokens`` path
     produced: int = 0
+    adapter: Optional[str] = None    # the LoRA adapter of every forward row of this sequence
 
     def advance(self, toks) -> bool:
         """Take the tokens of one round, of which only the last can end the stream; whether it did."""
@@ -125,19 +126,25 @@ def decode_round(model, cache, slots, proposer, num_draft, stats, sample=sample_
 
     ``draft_for`` caps a draft at ``max_new_tokens - produced - 1`` tokens, so the cached length
     stays below prompt + ``max_new_tokens``, which is what the sequence's blocks were sized (in the
-    engine: reserved) for; the extend cannot run out of blocks."""
+    engine: reserved) for; the extend cannot run out of blocks.
+
+    If some live stream has a LoRA ``adapter``, both calls carry ``adapters=[...]`` (one per row of
+    ``decode_step``, one per sequence of ``extend``); otherwise the keyword is not passed at all."""
     live = [s for s, st in enumerate(slots) if st is not None]
     if not live:
         return []
     drafts = [draft_for(proposer, num_draft, slots[s].history, slots[s].produced, slots[s].max_new_tokens)
               if proposer is not None else [] for s in live]
+    lora = any(slots[s].adapter is not None for s in live)
     if not any(drafts):
+        akw = {"adapters": [st.adapter if st is not None else None for st in slots]} if lora else {}
         logits = model.decode_step([st.history[-1] if st is not None else 0 for st in slots], cache,
-                                   [st.seq_id if st is not None else None for st in slots])
+                                   [st.seq_id if st is not None else None for st in slots], **akw)
         toks = sample(logits, [(slots[s], s) for s in live])
         return [(s, [tok], slots[s].advance([tok])) for s, tok in zip(live, toks)]
     rows = [[slots[s].history[-1]] + draft for s, draft in zip(live, drafts)]
-    logits = model.extend(rows, cache, [slots[s].seq_id for s in live], all_logits=True, num_splits=None)
+    akw = {"adapters": [slots[s].adapter for s in live]} if lora else {}
+    logits = model.extend(rows, cache, [slots[s].seq_id for s in live], all_logits=True, num_splits=None, **akw)
     sampled = _sample_fused(logits, [(slots[s], slots[s].produced + j) for s, row in zip(live, rows)
                                      for j in range(len(row))])
     stats["verify_steps"] += 1

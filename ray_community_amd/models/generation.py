@@ -54,6 +54,7 @@ class _Prefix:
     users: int = 0           # requests accepted with this prefix whose prefill is not over
     reserved: bool = False   # its blocks are counted in the admission budget
     released: bool = False
+    adapter: Optional[str] = None   # the LoRA adapter its K/V was computed with
 
 
 _NO_LIMIT = 1 << 62
@@ -100,10 +101,33 @@ class GenerationEngine:
         self._ids = itertools.count()
 
     # -------------------------------------------------------------------------------- requests
-    def register_prefix(self, tokens) -> int:
+    def _check_adapter(self, adapter):
+        if adapter is not None and adapter not in getattr(self.model, "loaded_adapters", lambda: [])():
+            raise ValueError(f"unknown adapter {adapter!r}: load it first (load_adapter)")
+
+    def load_adapter(self, name, adapter):
+        """``Llama.load_adapter`` on the engine's model."""
+        return self.model.load_adapter(name, adapter)
+
+    def adapter_users(self, name) -> int:
+        """Waiting and active requests and registered prefixes that use adapter ``name``."""
+        reqs = [r for r in list(self.waiting) + self.slots if r is not None]
+        return sum(o.adapter == name for o in reqs + list(self._prefixes.values()))
+
+    def unload_adapter(self, name):
+        """Free the adapter's slot; refused while a request or a registered prefix uses it."""
+        users = self.adapter_users(name)
+        if users:
+            raise RuntimeError(f"adapter {name!r} is in use by {users} request(s) / prefix(es)")
+        self.model.unload_adapter(name)
+
+    def register_prefix(self, tokens, adapter: Optional[str] = None) -> int:
         """Register a prompt prefix (system prompt, few-shot header) that requests can share;
         returns its handle. The prefix is prefilled once into a pinned sequence, lazily, by the
-        first ``step()`` that needs it and through the same ``prefill_chunk`` budget."""
+        first ``step()`` that needs it and through the same ``prefill_chunk`` budget. Its cached K/V
+        belongs to ``adapter`` (a loaded LoRA adapter or ``None``): requests naming the prefix must
+        name the same adapter."""
+        self._check_adapter(adapter)
         tokens = [int(t) for t in tokens]
         if not tokens:
             raise ValueError("a prefix needs at least one token")
@@ -112,7 +136,7 @@ class GenerationEngine:
                              f"{self.model.cfg.max_seq_len}")
         handle = next(self._ids)
         self._prefixes[handle] = _Prefix(handle, tokens, ("engine-prefix", id(self), handle),
-                                         -(-len(tokens) // self.cache.page_size))
+                                         -(-len(tokens) // self.cache.page_size), adapter=adapter)
         return handle
 
     def release_prefix(self, handle: int) -> None:
@@ -136,7 +160,8 @@ class GenerationEngine:
             self._drop_prefix_if_unused(pfx)
 
     def add_request(self, prompt, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
-                    seed=None, prefix: Optional[int] = None, top_p: float = 1.0, min_p: float = 0.0) -> int:
+                    seed=None, prefix: Optional[int] = None, top_p: float = 1.0, min_p: float = 0.0,
+                    adapter: Optional[str] = None) -> int:
         """Queue a request; returns its id. It is admitted by a later ``step()`` once a slot is
         free and the cache can hold its whole sequence (prompt + ``max_new_tokens``). With
         ``prefix`` (a ``register_prefix`` handle) ``prompt`` is the suffix after that prefix: the
@@ -144,7 +169,11 @@ class GenerationEngine:
 
         ``top_p`` / ``min_p`` (``ops.sample_logits``) or the engine's ``fused_sampling`` put the
         request on the batched sampler: all such rows of a step's logits are sampled by one call,
-        each with ``seed`` (0 if ``None``) and its own count of produced tokens as the step."""
+        each with ``seed`` (0 if ``None``) and its own count of produced tokens as the step.
+
+        ``adapter``: a loaded LoRA adapter's name (``Llama.load_adapter``); every forward row of the
+        request is routed to it. With a ``prefix`` it must be the prefix's adapter."""
+        self._check_adapter(adapter)
         sampling = Sampling(temperature, top_k, top_p, min_p, seed, self.fused_sampling)
         prompt = [int(t) for t in prompt]
         if not prompt or max_new_tokens < 1:
@@ -154,6 +183,9 @@ class GenerationEngine:
             pfx = self._prefixes.get(prefix)
             if pfx is None:
                 raise ValueError(f"unknown or released prefix handle {prefix!r}")
+            if pfx.adapter != adapter:
+                raise ValueError(f"prefix {prefix!r} was registered with adapter {pfx.adapter!r}, the request names "
+                                 f"{adapter!r}: cached K/V belongs to the adapter it was computed with")
         page = self.cache.page_size
         whole = len(pfx.tokens) // page * page if pfx is not None else 0
         total = (len(pfx.tokens) if pfx is not None else 0) + len(prompt) + int(max_new_tokens)
@@ -171,7 +203,7 @@ class GenerationEngine:
         rid = next(self._ids)
         req = _Request(seq_id=("engine", id(self), rid), history=list(prompt), max_new_tokens=int(max_new_tokens),
                        sampling=sampling, eos_token_id=eos_token_id, generator=gen, rid=rid, blocks=blocks,
-                       feed=prompt)
+                       feed=prompt, adapter=adapter)
         if pfx is not None:
             req.prefix = pfx
             pfx.users += 1
@@ -255,13 +287,15 @@ class GenerationEngine:
 
     def _feed(self, call, items, events):
         """One prefill call over ``items`` ``(slot or None, request or prefix, tokens)``:
-        ``call(token lists, cache, seq_ids)`` gives one logits row per item. A request whose prompt
+        ``call(token lists, cache, seq_ids)`` gives one logits row per item (it gets ``adapters=``
+        only if an item has a LoRA adapter). A request whose prompt
         is now cached emits its first token and retires or stays; returns the ids of those that
         stay. If the call fails it cached nothing (it is all or nothing): its requests go back to
         the head of the queue in arrival order, so no slot decodes a sequence that was never
         prefilled."""
         try:
-            logits = call([t for _, _, t in items], self.cache, [o.seq_id for _, o, _ in items])
+            akw = {"adapters": [o.adapter for _, o, _ in items]} if any(o.adapter is not None for _, o, _ in items) else {}
+            logits = call([t for _, _, t in items], self.cache, [o.seq_id for _, o, _ in items], **akw)
         except Exception:
             self._requeue([slot for slot, _, _ in items if slot is not None])
             raise
@@ -290,7 +324,7 @@ class GenerationEngine:
             plain = [(s, r, r.feed) for s, r in enumerate(self.slots)
                      if r is not None and r.prefilling and r.prefix is None]
             if plain:
-                self._feed(lambda toks, cache, ids: self.model.prefill(toks, None, cache, ids), plain, events)
+                self._feed(lambda toks, cache, ids, **kw: self.model.prefill(toks, None, cache, ids, **kw), plain, events)
         pre = sorted((s for s, r in enumerate(self.slots) if r is not None and r.prefilling),
                      key=lambda s: self.slots[s].rid)
         budget = self.prefill_chunk if self.prefill_chunk is not None else _NO_LIMIT

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..parallel.fused_linear import FusedEmbedding, FusedWgradLinear, swiglu_down
+from . import lora as _lora
 from .quant import QuantLinear, quantize_weights_
 
 
@@ -127,7 +128,7 @@ class MLP(nn.Module):
         # On the flat-gradient GPU path SwiGLU also writes act^T (the down projection's wgrad
         # operand), and the backward's down dgrad GEMM applies the SwiGLU backward in its epilogue,
         # writing d(gate|up) and its transpose for the gate_up wgrad (parallel/fused_linear.py).
-        if isinstance(self.down, QuantLinear):  # fp8 weights (inference only): the two separate ops
+        if isinstance(self.down, (QuantLinear, _lora.LoraLinear)):  # fp8 weights / LoRA (inference only): the two separate ops
             return self.down(ops.swiglu(self.gate_up(x)))
         return swiglu_down(self.gate_up(x), self.down)
 
@@ -171,6 +172,27 @@ class Llama(nn.Module):
         halves their bytes; ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run
         ``ops.linear_w8``. Idempotent. Training paths are not available afterwards."""
         return quantize_weights_(self, dtype)
+
+    def enable_lora_(self, max_adapters: int, max_rank: int):
+        """Make room for ``max_adapters`` LoRA adapters of up to ``max_rank`` per projection
+        (``models/lora.py``): ``qkv``, ``o``, ``gate_up`` and ``down`` of every block become
+        ``LoraLinear``s around their base modules (before or after ``quantize_weights_``), and
+        ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` take ``adapters=``. With no adapter
+        named every logit keeps its bits. Training paths are not available afterwards."""
+        return _lora.enable_lora_(self, max_adapters, max_rank)
+
+    def load_adapter(self, name, adapter):
+        """Copy a ``LoraAdapter`` into a free slot under ``name``. ``AdapterSlotsFull`` when there is
+        none; ``ValueError`` on a rank above ``max_rank``, a shape mismatch or a duplicate name."""
+        return _lora.load_adapter(self, name, adapter)
+
+    def unload_adapter(self, name):
+        return _lora.unload_adapter(self, name)
+
+    def loaded_adapters(self):
+        """Names of the loaded adapters (empty without ``enable_lora_``)."""
+        bank = getattr(self, "lora", None)
+        return sorted(bank.slots, key=bank.slots.get) if bank is not None else []
 
     def rope_table(self, device):
         key = str(device)
@@ -238,12 +260,13 @@ class Llama(nn.Module):
             raise
         return slots
 
-    def _cached_forward(self, tokens, cache, slots, rope, attend, rows=None):
+    def _cached_forward(self, tokens, cache, slots, rope, attend, rows=None, adapters=None):
         """The body of a forward over ``cache``: embed the flat ``tokens`` ``[T]``, run the layers
         and return the logits of ``rows`` (indices into ``T``; ``None``: every row). Each layer
         rotates its fused qkv with ``rope = (seq_len, positions)`` (``ops.apply_rope_``), appends
         K/V at ``slots`` ``[T]`` and takes ``attend(i, blk, qkv)`` (which may read q in place from
-        the fused rows) as the projected attention output ``[T, H]``."""
+        the fused rows) as the projected attention output ``[T, H]``. ``adapters``: a LoRA adapter
+        name or ``None`` per row of ``tokens``, routed for the duration of the call."""
         cfg = self.cfg
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
         cs = self.rope_table(tokens.device)
@@ -255,18 +278,20 @@ class Llama(nn.Module):
             ops.kv_cache_append_(cache.k[i], cache.v[i], qkv, slots, Hq, Hk, D, k_scale=ks, v_scale=vs)
             return attend(i, blk, qkv)
 
-        h = self._run_layers(self.embed(tokens), attn)
+        with _lora.route(self, adapters, tokens.device):
+            h = self._run_layers(self.embed(tokens), attn)
         return self.logits(h if rows is None else h[rows])
 
     @torch.inference_mode()
-    def prefill(self, tokens, lengths, cache, seq_ids):
+    def prefill(self, tokens, lengths, cache, seq_ids, *, adapters=None):
         """Run the prompts through the model, fill ``cache`` and return the logits ``[B, V]`` of
         each sequence's last real token.
 
         ``tokens``: ``[B, S]`` right-padded token ids (or a list of token lists, then ``lengths``
         may be ``None``); ``lengths``: real length per row. The batch is right-padded to a
         multiple of 128 and run through the ordinary causal forward (right padding cannot reach a
-        real token through a causal mask); padded tokens get slot -1, i.e. are not cached."""
+        real token through a causal mask); padded tokens get slot -1, i.e. are not cached.
+        ``adapters``: a loaded LoRA adapter's name or ``None`` per sequence (``enable_lora_``)."""
         cfg = self.cfg
         dev = self.embed.weight.device
         if not torch.is_tensor(tokens):
@@ -276,8 +301,8 @@ class Llama(nn.Module):
             tokens = torch.tensor([r + [0] * (width - len(r)) for r in rows], dtype=torch.long)
         lengths = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         B = tokens.shape[0]
-        if len(lengths) != B or len(seq_ids) != B:
-            raise ValueError("tokens, lengths and seq_ids must agree on the batch size")
+        if len(lengths) != B or len(seq_ids) != B or (adapters is not None and len(adapters) != B):
+            raise ValueError("tokens, lengths, seq_ids and adapters must agree on the batch size")
         if min(lengths) < 1 or max(lengths) > tokens.shape[1]:
             raise ValueError("every prompt needs between 1 and tokens.shape[1] tokens")
         S = -(-max(lengths) // 128) * 128
@@ -291,21 +316,24 @@ class Llama(nn.Module):
             slots[b, :len(s)] = torch.tensor(s, dtype=torch.int32)
         slots = slots.reshape(-1).to(dev)
         last = torch.tensor([b * S + n - 1 for b, n in enumerate(lengths)], dtype=torch.long, device=dev)
+        if adapters is not None:  # per row; the padding rows take none
+            adapters = [a if s < n else None for a, n in zip(adapters, lengths) for s in range(S)]
         # the B x S x V logits are never formed
         return self._cached_forward(padded.view(-1), cache, slots, (S, None),
-                                    lambda i, blk, qkv: blk.attn.causal_attention(qkv, B, S), last)
+                                    lambda i, blk, qkv: blk.attn.causal_attention(qkv, B, S), last, adapters)
 
     @torch.inference_mode()
-    def decode_step(self, tokens, cache, seq_ids):
+    def decode_step(self, tokens, cache, seq_ids, *, adapters=None):
         """One new token per sequence: append its K/V to ``cache`` and return logits ``[B, V]``.
         A ``None`` in ``seq_ids`` is an inactive slot of a fixed-size batch (context length 0,
-        nothing cached; its logits row is meaningless)."""
+        nothing cached; its logits row is meaningless). ``adapters``: a LoRA adapter name or
+        ``None`` per row."""
         cfg = self.cfg
         dev = self.embed.weight.device
         tokens = torch.as_tensor(tokens, dtype=torch.long).reshape(-1).to(dev)
         B = tokens.shape[0]
-        if len(seq_ids) != B:
-            raise ValueError("tokens and seq_ids must agree on the batch size")
+        if len(seq_ids) != B or (adapters is not None and len(adapters) != B):
+            raise ValueError("tokens, seq_ids and adapters must agree on the batch size")
         pos = [cache.length(s) if s is not None else 0 for s in seq_ids]
         if max(pos) >= cfg.max_seq_len:
             raise ValueError(f"sequence would exceed max_seq_len {cfg.max_seq_len}")
@@ -320,14 +348,15 @@ class Llama(nn.Module):
             return blk.attn.o(ops.paged_attention_decode(qkv, cache.k[i], cache.v[i], block_table, context_lens,
                                                          Hq, Hk, D, k_scale=ks, v_scale=vs))
 
-        return self._cached_forward(tokens, cache, slots, (1, positions), attend)
+        return self._cached_forward(tokens, cache, slots, (1, positions), attend, None, adapters)
 
     @torch.inference_mode()
-    def extend(self, tokens, cache, seq_ids, all_logits: bool = False, num_splits=1):
+    def extend(self, tokens, cache, seq_ids, all_logits: bool = False, num_splits=1, *, adapters=None):
         """Append several new tokens to each sequence and return the logits ``[B, V]`` of each
         sequence's last new token, or with ``all_logits`` the logits ``[sum(len), V]`` of every fed
         row in packed order (draft verification). ``num_splits`` goes to
-        ``ops.paged_attention_extend`` (``None``: its heuristic).
+        ``ops.paged_attention_extend`` (``None``: its heuristic). ``adapters``: a LoRA adapter name
+        or ``None`` per sequence, applied to each of its rows.
 
         ``tokens`` is a list of non-empty token lists; each ``seq_id`` may be new or already cached
         at any length (a prompt chunk, a further chat turn, draft tokens to verify). The batch is
@@ -338,8 +367,8 @@ class Llama(nn.Module):
         dev = self.embed.weight.device
         rows = [[int(t) for t in r] for r in tokens]
         B = len(rows)
-        if len(seq_ids) != B:
-            raise ValueError("tokens and seq_ids must agree on the batch size")
+        if len(seq_ids) != B or (adapters is not None and len(adapters) != B):
+            raise ValueError("tokens, seq_ids and adapters must agree on the batch size")
         if B == 0 or min(len(r) for r in rows) < 1:
             raise ValueError("extend needs at least one sequence and at least one new token per sequence")
         if len(set(seq_ids)) != B:
@@ -365,12 +394,14 @@ class Llama(nn.Module):
                                                          k_scale=ks, v_scale=vs))
 
         last = None if all_logits else torch.tensor([c - 1 for c in cu[1:]], dtype=torch.long, device=dev)
-        return self._cached_forward(flat, cache, slots, (1, positions), attend, last)
+        if adapters is not None:
+            adapters = [a for a, r in zip(adapters, rows) for _ in r]
+        return self._cached_forward(flat, cache, slots, (1, positions), attend, last, adapters)
 
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
                  seed=None, cache=None, prefill_chunk=None, top_p: float = 1.0, min_p: float = 0.0,
-                 fused_sampling: bool = False, speculative=None, kv_cache_dtype=None):
+                 fused_sampling: bool = False, speculative=None, kv_cache_dtype=None, adapters=None):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
@@ -396,7 +427,10 @@ class Llama(nn.Module):
         (a ``cache`` passed in keeps its own). Under fp8, ``prefill`` attends over the fresh,
         unquantised K/V while ``extend`` and ``decode_step`` read the quantised cache, so a
         ``prefill_chunk`` stream may differ from the unchunked one. The speculative guarantee
-        holds: the verify ``extend`` and ``decode_step`` read the same quantised bytes."""
+        holds: the verify ``extend`` and ``decode_step`` read the same quantised bytes.
+
+        ``adapters``: one loaded LoRA adapter name or ``None`` per prompt (``enable_lora_``,
+        ``load_adapter``); every forward call of the request routes that sequence's rows to it."""
         from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows, sample_tokens
         from .kv_cache import PagedKVCache
         from .speculative import new_stats, resolve_speculative
@@ -406,6 +440,11 @@ class Llama(nn.Module):
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         prompts = [list(p) for p in prompts]
+        if adapters is not None and len(adapters) != len(prompts):
+            raise ValueError("adapters needs one entry per prompt")
+        if adapters is not None and all(a is None for a in adapters):
+            adapters = None
+        akw = {} if adapters is None else {"adapters": list(adapters)}
         if not prompts or max_new_tokens <= 0:
             return [[] for _ in prompts]
         dev = self.embed.weight.device
@@ -427,7 +466,8 @@ class Llama(nn.Module):
                 return [nxt[row] for _, row in picks]
 
         ids = [("generate", next(_SEQ_IDS)) for _ in prompts]
-        streams = [Stream(sid, list(p), max_new_tokens, sampling, eos_token_id) for sid, p in zip(ids, prompts)]
+        streams = [Stream(sid, list(p), max_new_tokens, sampling, eos_token_id, adapter=a)
+                   for sid, p, a in zip(ids, prompts, adapters or [None] * len(prompts))]
         slots = list(streams)
         stats = new_stats()
         if proposer is not None:
@@ -441,9 +481,9 @@ class Llama(nn.Module):
 
         try:
             if prefill_chunk is None:
-                logits = self.prefill(prompts, None, cache, ids)
+                logits = self.prefill(prompts, None, cache, ids, **akw)
             else:
-                logits = self._chunked_prefill(prompts, cache, ids, int(prefill_chunk))
+                logits = self._chunked_prefill(prompts, cache, ids, int(prefill_chunk), adapters)
             first = sample(logits, [(st, b) for b, st in enumerate(streams)])
             settle([(b, [tok], st.advance([tok])) for b, (st, tok) in enumerate(zip(streams, first))])
             while any(st is not None for st in slots):
@@ -453,12 +493,13 @@ class Llama(nn.Module):
                 cache.free(sid)
         return [st.history[len(p):] for st, p in zip(streams, prompts)]
 
-    def _chunked_prefill(self, prompts, cache, ids, chunk):
+    def _chunked_prefill(self, prompts, cache, ids, chunk, adapters=None):
         """``prefill`` through ``extend``: ``chunk`` tokens per unfinished prompt per call."""
         logits = [None] * len(prompts)
         for off in range(0, max(len(p) for p in prompts), chunk):
             idx = [b for b, p in enumerate(prompts) if off < len(p)]
-            lg = self.extend([prompts[b][off: off + chunk] for b in idx], cache, [ids[b] for b in idx])
+            akw = {} if adapters is None else {"adapters": [adapters[b] for b in idx]}
+            lg = self.extend([prompts[b][off: off + chunk] for b in idx], cache, [ids[b] for b in idx], **akw)
             for j, b in enumerate(idx):
                 if off + chunk >= len(prompts[b]):
                     logits[b] = lg[j]

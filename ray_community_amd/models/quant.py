@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops import reference as ref
+from .lora import LoraLinear
 
 WEIGHT_DTYPES = (None, "auto", "fp8")
 
@@ -70,6 +71,8 @@ def quantize_weights_(model, dtype="fp8"):
         for blk in model.layers:
             for parent, name in ((blk.attn, "qkv"), (blk.attn, "o"), (blk.mlp, "gate_up"), (blk.mlp, "down")):
                 lin = getattr(parent, name)
+                if isinstance(lin, LoraLinear):  # LoRA enabled first: quantise the wrapped base
+                    parent, name, lin = lin, "base", lin.base
                 if not isinstance(lin, QuantLinear):
                     setattr(parent, name, QuantLinear.from_weight(lin.weight))
         if not isinstance(model.lm_head, QuantLinear):

@@ -47,6 +47,9 @@ __all__ = [
     "linear_w8",
     "linear_w8_supported",
     "dequant_w8",
+    "lora_routing",
+    "lora_supported",
+    "lora_add_",
     "kernels_available",
 ]
 
@@ -1531,3 +1534,108 @@ def linear_w8(x, qweight, scale, out=None):
         out.copy_(y)
         return out
     return y.view(*lead, N)
+
+
+# ----------------------------------------------------------------------------------- multi-LoRA
+LORA_TILE = 16  # rows of one adapter slot per routing tile: the MFMA's column count (ops/csrc/lora.hip)
+
+
+class LoraRouting:
+    """Which adapter slot each row of one forward call takes (``lora_routing``). ``idx [M]`` int32 is
+    the slot per row (-1: none); ``tile_slot [n_tiles]`` and ``tile_rows [n_tiles, 16]`` (-1: padding)
+    group the rows with a slot into tiles of up to 16 rows of one slot; ``any`` is false when every
+    row is a base row. The three arrays are views of one device tensor: one upload per call."""
+    __slots__ = ("idx", "tile_slot", "tile_rows", "n_tiles", "any", "num_rows")
+
+    def __init__(self, idx, tile_slot, tile_rows):
+        self.idx, self.tile_slot, self.tile_rows = idx, tile_slot, tile_rows
+        self.n_tiles, self.num_rows = int(tile_slot.shape[0]), int(idx.shape[0])
+        self.any = self.n_tiles > 0
+
+
+def lora_routing(adapters, device=None):
+    """The routing of a batch whose row ``m`` takes adapter slot ``adapters[m]`` (``-1`` or ``None``:
+    no adapter). Slots are taken in ascending order, the rows of a slot in ascending order, 16 to a
+    tile; the rows of a slot need not be contiguous. Built on the host and uploaded once."""
+    idx = [-1 if a is None else int(a) for a in adapters]
+    if any(a < -1 for a in idx):
+        raise ValueError("lora_routing: a slot is >= 0, or -1 / None for no adapter")
+    by_slot = {}
+    for m, a in enumerate(idx):
+        if a >= 0:
+            by_slot.setdefault(a, []).append(m)
+    tile_slot, tile_rows = [], []
+    for a in sorted(by_slot):
+        rows = by_slot[a]
+        for at in range(0, len(rows), LORA_TILE):
+            part = rows[at: at + LORA_TILE]
+            tile_slot.append(a)
+            tile_rows.extend(part + [-1] * (LORA_TILE - len(part)))
+    M, n = len(idx), len(tile_slot)
+    flat = torch.tensor(idx + tile_slot + tile_rows, dtype=torch.int32)
+    if device is not None:
+        flat = flat.to(device)
+    return LoraRouting(flat[:M], flat[M: M + n], flat[M + n:].view(n, LORA_TILE))
+
+
+def _lora_tensor_ok(t) -> bool:
+    if not (torch.is_tensor(t) and t.is_cuda and t.data_ptr() % 16 == 0):
+        return False
+    if t.dtype == torch.float32:  # the scales
+        return t.dim() == 1 and t.is_contiguous()
+    if t.dtype != torch.bfloat16:
+        return False
+    if t.dim() == 3:  # the bank
+        return t.is_contiguous()
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1]  # x / y views
+
+
+def lora_supported(M: int, N: int, K: int, R: int, *tensors) -> bool:
+    """What the LoRA kernels take: ``K % 128 == 0``, ``N % 16 == 0``, ``R % 16 == 0``, ``16 <= R <=
+    256``, ``M >= 1``; CUDA tensors with 16-byte aligned bases: bf16 2-D ``x`` / ``y`` with unit inner
+    stride and a row stride that is a multiple of 8, contiguous bf16 3-D banks, contiguous fp32 scales."""
+    return (M >= 1 and N > 0 and K > 0 and N % 16 == 0 and K % 128 == 0 and R % 16 == 0 and 16 <= R <= 256
+            and all(_lora_tensor_ok(t) for t in tensors))
+
+
+def _lora_kernel(y, x, A, B, scale, routing):
+    """The two launches on operands ``lora_supported`` accepts."""
+    (M, N), K = y.shape, x.shape[1]
+    S, R = A.shape[0], A.shape[1]
+    L = lib()
+    splits = L.rca_lora_splits(K, R)
+    ws = _workspace(y.device, "lora_partials", splits * routing.n_tiles * LORA_TILE * R)
+    check(L.rca_lora_add(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), A.data_ptr(), B.data_ptr(),
+                         scale.data_ptr(), routing.tile_slot.data_ptr(), routing.tile_rows.data_ptr(), routing.n_tiles,
+                         ws.data_ptr(), ws.numel() * 4, M, N, K, R, S, stream_ptr(y.device)), "lora_add")
+    return y
+
+
+def lora_add_(y, x, A, B, scale, routing):
+    """Add each row's LoRA update to the base output ``y [M, N]`` of a linear with input ``x [M, K]``,
+    in place; returns ``y``. ``A [S, R, K]``, ``B [S, N, R]`` and ``scale [S]`` (fp32) are the stacked
+    adapters of ``S`` slots of capacity ``R``; ``routing`` (``lora_routing``) names the slot of every
+    row. ``reference.lora_add_ref`` has the arithmetic: ``t = A x`` accumulated in fp32 and rounded to
+    bf16 once, ``y + scale * B t`` accumulated in fp32 and rounded once; rows without an adapter keep
+    their bits. No autograd: inference only.
+
+    bf16 CUDA operands within ``lora_supported`` run the two gfx950 kernels of ``ops/csrc/lora.hip``
+    (an output row depends on its own input row and its slot only, bitwise, whatever the batch is); an
+    ``x`` with a non-unit inner stride or a misaligned base is made contiguous first. CPU tensors,
+    other dtypes and shapes outside the contract run the reference. With ``routing.any`` false nothing
+    is launched."""
+    if y.dim() != 2 or x.dim() != 2 or A.dim() != 3 or B.dim() != 3:
+        raise ValueError("lora_add_: y [M, N], x [M, K], A [S, R, K] and B [S, N, R] are expected")
+    (M, N), K = y.shape, x.shape[1]
+    S, R = A.shape[0], A.shape[1]
+    if (x.shape[0] != M or A.shape[2] != K or tuple(B.shape) != (S, N, R) or tuple(scale.shape) != (S,)
+            or routing.num_rows != M):
+        raise ValueError(f"lora_add_: y {tuple(y.shape)}, x {tuple(x.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)}, "
+                         f"scale {tuple(scale.shape)} and a routing of {routing.num_rows} rows do not agree")
+    if not routing.any:
+        return y
+    if x.is_cuda and x.dtype == torch.bfloat16 and not _lora_tensor_ok(x):
+        x = x.contiguous()
+    if lora_supported(M, N, K, R, y, x, A, B, scale) and routing.idx.device == y.device:
+        return _lora_kernel(y, x, A, B, scale, routing)
+    return ref.lora_add_ref(y, x, A, B, scale, routing.idx)

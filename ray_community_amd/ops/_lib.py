@@ -95,6 +95,9 @@ _SIGS = {
     "rca_linear_w8_splits": (c_int, [c_int, c_int]),
     "rca_linear_w8a16": (c_int, [c_void_p] * 5 + [c_ll, c_int, c_int, c_int, c_ll, c_ll, c_void_p]),
     "rca_dequant_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "rca_lora_splits": (c_int, [c_int, c_int]),
+    "rca_lora_add": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_int, c_void_p, c_ll] + [c_int] * 5
+                     + [c_void_p]),
 }
 
 

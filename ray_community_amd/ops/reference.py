@@ -201,6 +201,23 @@ def linear_w8_ref(x, qweight, scale):
     return torch.nn.functional.linear(x, kv_dequantize_fp8_ref(qweight, scale, x.dtype))
 
 
+def lora_add_ref(y, x, A, B, scale, idx):
+    """Per-row LoRA update, in place on ``y [M, N]``: with ``a = idx[m] >= 0`` the adapter slot of row
+    ``m`` (``A [S, R, K]``, ``B [S, N, R]``, ``scale [S]`` fp32),
+
+        t[m, :] = bf16(sum_k A[a, :, k] * x[m, k])
+        y[m, n] = y.dtype(float(y[m, n]) + scale[a] * sum_r B[a, n, r] * t[m, r])
+
+    both sums in fp32. A row with ``idx[m] < 0`` is not touched. The contract of ``ops.lora_add_``
+    and its path for CPU tensors, other dtypes and shapes outside the kernel's contract."""
+    idx = idx.reshape(-1).long()
+    for s in torch.unique(idx[idx >= 0]).tolist():
+        rows = (idx == s).nonzero().reshape(-1).to(y.device)
+        t = (x[rows].float() @ A[s].float().t()).bfloat16().float()
+        y[rows] = (y[rows].float() + scale[s].float() * (t @ B[s].float().t())).to(y.dtype)
+    return y
+
+
 def kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D, k_scale=None, v_scale=None):
     """Copy the K and V heads of each token of the fused (already rotated) ``qkv``
     ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]`` at slot

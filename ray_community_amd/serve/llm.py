@@ -22,7 +22,7 @@ class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
                  num_blocks=None, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
                  prefill_chunk=None, fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
-                 cache_bytes=None, weight_dtype=None):
+                 cache_bytes=None, weight_dtype=None, lora=None, adapters=None):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
         ``torch.save``d state dict (without one the weights are initialised from ``seed``);
         ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
@@ -35,16 +35,26 @@ class _LlamaDeployment:
         (``"fp8"``: quantised pages, about half the bytes per token) picks its dtype, as in
         ``GenerationEngine``; ``weight_dtype`` (``None`` / ``"auto"`` / ``"fp8"``): ``"fp8"`` quantises
         the linears' weights once the state dict is loaded (``Llama.quantize_weights_``: half the
-        weight bytes, activations stay in ``dtype``)."""
+        weight bytes, activations stay in ``dtype``); ``lora={"max_adapters": n, "max_rank": r}``
+        makes room for LoRA adapters (``Llama.enable_lora_``, after the quantisation) that requests
+        select by name, and ``adapters={"name": path}`` preloads ``LoraAdapter.save``d files."""
         import torch
 
-        from ..models import GenerationEngine, build_llama, weight_bytes
+        from ..models import GenerationEngine, LoraAdapter, build_llama, weight_bytes
 
         torch.manual_seed(seed)
         self.model = build_llama(model, device=device, dtype=getattr(torch, dtype) if isinstance(dtype, str) else dtype)
         if state_dict_path is not None:
             self.model.load_state_dict(torch.load(state_dict_path, map_location=device))
         self.model.quantize_weights_(weight_dtype)
+        self.lora = None
+        if lora is not None:
+            self.lora = {"max_adapters": int(lora["max_adapters"]), "max_rank": int(lora["max_rank"])}
+            self.model.enable_lora_(**self.lora)
+        elif adapters:
+            raise ValueError("adapters= needs lora={'max_adapters': n, 'max_rank': r}")
+        for name, path in (adapters or {}).items():
+            self.model.load_adapter(name, LoraAdapter.load(path))
         self.model.eval()
         self.weight_dtype = "fp8" if weight_dtype == "fp8" else None
         self.weight_bytes = weight_bytes(self.model)
@@ -83,16 +93,22 @@ class _LlamaDeployment:
             self._driver = None
 
     async def generate(self, prompt_tokens, max_new_tokens=None, temperature: float = 0.0, top_k: int = 0,
-                       eos_token_id=None, seed=None, top_p: float = 1.0, min_p: float = 0.0):
+                       eos_token_id=None, seed=None, top_p: float = 1.0, min_p: float = 0.0, adapter=None):
         """Async generator of the new token ids of one request (sampling arguments as in
-        ``GenerationEngine.add_request``)."""
+        ``GenerationEngine.add_request``). ``adapter``: the name of a loaded LoRA adapter; without
+        one, a non-empty ``serve.get_multiplexed_model_id()`` of the request is the name."""
+        from .multiplex import get_multiplexed_model_id
+
+        if adapter is None and self.lora is not None:
+            adapter = get_multiplexed_model_id() or None
         loop = asyncio.get_running_loop()
         n = self.default_max_new_tokens if max_new_tokens is None else int(max_new_tokens)
         q = asyncio.Queue()
 
         def add():  # on the engine thread, so no step can run between queueing and registering
             rid = self.engine.add_request(list(prompt_tokens), n, temperature=temperature, top_k=top_k,
-                                          eos_token_id=eos_token_id, seed=seed, top_p=top_p, min_p=min_p)
+                                          eos_token_id=eos_token_id, seed=seed, top_p=top_p, min_p=min_p,
+                                          **({} if adapter is None else {"adapter": adapter}))
             self._queues[rid] = [q, n, 0]
             return rid
 
@@ -114,6 +130,20 @@ class _LlamaDeployment:
                 self._cancelled += 1
                 loop.run_in_executor(self._exec, self.engine.cancel, rid)
 
+    async def load_adapter(self, name, path):
+        """Load a ``LoraAdapter.save``d file under ``name`` (on the engine thread, between steps)."""
+        from ..models import LoraAdapter
+
+        loop = asyncio.get_running_loop()
+        await loop.run_in_executor(self._exec, lambda: self.engine.load_adapter(name, LoraAdapter.load(path)))
+        return self.model.loaded_adapters()
+
+    async def unload_adapter(self, name):
+        """Free an adapter's slot; fails while a request or a prefix uses it."""
+        loop = asyncio.get_running_loop()
+        await loop.run_in_executor(self._exec, self.engine.unload_adapter, name)
+        return self.model.loaded_adapters()
+
     async def status(self):
         """Engine occupancy and, per open stream, how far it is: ``{"active", "waiting", "streams":
         [{"request_id", "max_new_tokens", "produced"}], "cancelled"}``; a deployment with
@@ -121,7 +151,8 @@ class _LlamaDeployment:
         their prompt), one with ``fused_sampling`` adds ``"fused_sampling": True``, one with
         ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``, one with an fp8
         cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``, one with fp8
-        weights adds ``"weight_dtype": "fp8"`` and ``"weight_bytes"`` (the model's parameters and buffers)."""
+        weights adds ``"weight_dtype": "fp8"`` and ``"weight_bytes"`` (the model's parameters and buffers),
+        one with ``lora`` adds ``"lora": {"max_adapters", "max_rank", "loaded": [...], "bank_bytes"}``."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
                    for rid, e in list(self._queues.items())]
         st = {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
@@ -137,13 +168,18 @@ class _LlamaDeployment:
             st.update(kv_cache_dtype="fp8", num_blocks=cache.num_blocks, cache_bytes=cache.nbytes)
         if self.weight_dtype is not None:
             st.update(weight_dtype=self.weight_dtype, weight_bytes=self.weight_bytes)
+        if self.lora is not None:
+            from ..models.lora import bank_bytes
+
+            st.update(lora={**self.lora, "loaded": self.model.loaded_adapters(), "bank_bytes": bank_bytes(self.model)})
         return st
 
     async def __call__(self, request):
         """HTTP: JSON body ``{"prompt_tokens": [...], "max_new_tokens": n}`` (optionally
-        ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``eos_token_id``, ``seed``) -> newline-delimited token ids."""
+        ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``eos_token_id``, ``seed``, ``adapter``) -> newline-delimited token ids."""
         body = json.loads(await request.body())
-        kw = {k: body[k] for k in ("max_new_tokens", "temperature", "top_k", "top_p", "min_p", "eos_token_id", "seed")
+        kw = {k: body[k] for k in ("max_new_tokens", "temperature", "top_k", "top_p", "min_p", "eos_token_id", "seed",
+                                          "adapter")
               if k in body}
 
         async def lines():
