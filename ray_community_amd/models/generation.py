@@ -86,6 +86,7 @@ class GenerationEngine:
         self.fused_sampling = bool(fused_sampling) or self._proposer is not None
         self.spec_stats = new_stats()
         self._prefixes = {}
+        self._logprobs = {}   # request id -> entries not popped yet (requests with ``logprobs`` only)
         self.model = model
         w = model.embed.weight
         if cache is None:
@@ -161,7 +162,8 @@ class GenerationEngine:
 
     def add_request(self, prompt, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
                     seed=None, prefix: Optional[int] = None, top_p: float = 1.0, min_p: float = 0.0,
-                    adapter: Optional[str] = None) -> int:
+                    adapter: Optional[str] = None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                    frequency_penalty: float = 0.0, logprobs: Optional[int] = None) -> int:
         """Queue a request; returns its id. It is admitted by a later ``step()`` once a slot is
         free and the cache can hold its whole sequence (prompt + ``max_new_tokens``). With
         ``prefix`` (a ``register_prefix`` handle) ``prompt`` is the suffix after that prefix: the
@@ -172,9 +174,14 @@ class GenerationEngine:
         each with ``seed`` (0 if ``None``) and its own count of produced tokens as the step.
 
         ``adapter``: a loaded LoRA adapter's name (``Llama.load_adapter``); every forward row of the
-        request is routed to it. With a ``prefix`` it must be the prefix's adapter."""
+        request is routed to it. With a ``prefix`` it must be the prefix's adapter.
+
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` (``ops.penalize_logits``;
+        a shared prefix counts as prompt) and ``logprobs`` (``None``, or ``0..20`` alternatives per
+        token, fetched with ``pop_logprobs``) also put the request on the batched sampler."""
         self._check_adapter(adapter)
-        sampling = Sampling(temperature, top_k, top_p, min_p, seed, self.fused_sampling)
+        sampling = Sampling(temperature, top_k, top_p, min_p, seed, self.fused_sampling, repetition_penalty,
+                            presence_penalty, frequency_penalty, logprobs)
         prompt = [int(t) for t in prompt]
         if not prompt or max_new_tokens < 1:
             raise ValueError("a request needs a non-empty prompt and max_new_tokens >= 1")
@@ -209,6 +216,7 @@ class GenerationEngine:
             pfx.users += 1
             req.feed = pfx.tokens[whole:] + prompt  # the partly filled page is recomputed per request
             req.history = pfx.tokens + prompt
+            req.prompt_len = len(req.history)
         self.waiting.append(req)
         return rid
 
@@ -223,8 +231,15 @@ class GenerationEngine:
         for slot, req in enumerate(self.slots):
             if req is not None and req.rid == request_id:
                 self._retire(slot)
+                self._logprobs.pop(request_id, None)
                 return True
         return False
+
+    def pop_logprobs(self, request_id: int) -> list:
+        """The ``(token, logprob, [(id, logprob), ...])`` entries of a request with ``logprobs`` that
+        were produced since the last call, one per ``step()`` event of that request and in their
+        order; ``[]`` if there are none."""
+        return self._logprobs.pop(request_id, [])
 
     def has_work(self) -> bool:
         return bool(self.waiting) or any(r is not None for r in self.slots)
@@ -248,8 +263,11 @@ class GenerationEngine:
     def _emit(self, slot: int, toks, finished: bool, events):
         """The events of one request's tokens of one round (only the last can finish it); a
         finished request retires."""
-        rid = self.slots[slot].rid
+        req = self.slots[slot]
+        rid = req.rid
         events.extend((rid, tok, finished and n + 1 == len(toks)) for n, tok in enumerate(toks))
+        if req.sampling.logprobs is not None:
+            self._logprobs.setdefault(rid, []).extend(req.logprobs[-len(toks):])
         if finished:
             self._retire(slot)
 

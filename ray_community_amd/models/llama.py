@@ -401,7 +401,9 @@ class Llama(nn.Module):
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, temperature: float = 0.0, top_k: int = 0, eos_token_id=None,
                  seed=None, cache=None, prefill_chunk=None, top_p: float = 1.0, min_p: float = 0.0,
-                 fused_sampling: bool = False, speculative=None, kv_cache_dtype=None, adapters=None):
+                 fused_sampling: bool = False, speculative=None, kv_cache_dtype=None, adapters=None,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                 logprobs=None):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
@@ -430,13 +432,22 @@ class Llama(nn.Module):
         holds: the verify ``extend`` and ``decode_step`` read the same quantised bytes.
 
         ``adapters``: one loaded LoRA adapter name or ``None`` per prompt (``enable_lora_``,
-        ``load_adapter``); every forward call of the request routes that sequence's rows to it."""
+        ``load_adapter``); every forward call of the request routes that sequence's rows to it.
+
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` (``ops.penalize_logits``
+        has the exact rules; prompt and produced tokens count for repetition, produced tokens for the
+        other two) act on every step's logits before the draw, on the GPU. ``logprobs``: ``None``, or
+        the number ``0..20`` of alternatives to record per produced token; the call then returns
+        ``(tokens, logprobs)`` with one ``(token, logprob, [(id, logprob), ...])`` entry per token
+        (``ops.token_logprobs``: temperature 1, before top-k / top-p / min-p, after the penalties).
+        A non-neutral penalty or ``logprobs`` selects the batched sampler like ``fused_sampling``."""
         from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows, sample_tokens
         from .kv_cache import PagedKVCache
         from .speculative import new_stats, resolve_speculative
 
         proposer, num_draft = resolve_speculative(speculative)
-        sampling = Sampling(temperature, top_k, top_p, min_p, seed, fused_sampling or proposer is not None)
+        sampling = Sampling(temperature, top_k, top_p, min_p, seed, fused_sampling or proposer is not None,
+                            repetition_penalty, presence_penalty, frequency_penalty, logprobs)
         if prefill_chunk is not None and int(prefill_chunk) < 1:
             raise ValueError("prefill_chunk must be >= 1")
         prompts = [list(p) for p in prompts]
@@ -446,7 +457,7 @@ class Llama(nn.Module):
             adapters = None
         akw = {} if adapters is None else {"adapters": list(adapters)}
         if not prompts or max_new_tokens <= 0:
-            return [[] for _ in prompts]
+            return ([[] for _ in prompts], [[] for _ in prompts]) if logprobs is not None else [[] for _ in prompts]
         dev = self.embed.weight.device
         if max(len(p) for p in prompts) + max_new_tokens > self.cfg.max_seq_len:
             raise ValueError(f"prompt + max_new_tokens exceeds max_seq_len {self.cfg.max_seq_len}")
@@ -491,7 +502,8 @@ class Llama(nn.Module):
         finally:
             for sid in ids:
                 cache.free(sid)
-        return [st.history[len(p):] for st, p in zip(streams, prompts)]
+        out = [st.history[len(p):] for st, p in zip(streams, prompts)]
+        return (out, [st.logprobs for st in streams]) if logprobs is not None else out
 
     def _chunked_prefill(self, prompts, cache, ids, chunk, adapters=None):
         """``prefill`` through ``extend``: ``chunk`` tokens per unfinished prompt per call."""

@@ -44,6 +44,8 @@ __all__ = [
     "paged_extend_num_splits",
     "sample_logits",
     "sample_logits_supported",
+    "penalize_logits",
+    "token_logprobs",
     "linear_w8",
     "linear_w8_supported",
     "dequant_w8",
@@ -1435,6 +1437,145 @@ def sample_logits(logits, temperature, top_k=0, top_p=1.0, min_p=0.0, seeds=0, s
                                   params.data_ptr(), _p(uniforms), out.data_ptr(), B, V, stream_ptr(logits.device)),
           "rca_sample_logits")
     return out
+
+
+LOGPROBS_MAX_TOP = 20
+
+
+def check_penalty_params(repetition, presence, frequency):
+    """Raise ``ValueError`` naming the first penalty (lists of per-row values) out of range."""
+    import math
+
+    for r in repetition:
+        if not (math.isfinite(r) and r > 0):
+            raise ValueError(f"repetition must be finite and > 0, got {r!r}")
+    for name, vals in (("presence", presence), ("frequency", frequency)):
+        for v in vals:
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+
+
+def _check_logits(logits):
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise ValueError(f"logits must be a 2-D tensor [B, V], got "
+                         f"{tuple(logits.shape) if torch.is_tensor(logits) else type(logits).__name__}")
+    return logits.shape
+
+
+def penalize_logits(logits, tokens, ranges, repetition=1.0, presence=0.0, frequency=0.0):
+    """Repetition / presence / frequency penalties over per-row token histories, in one launch;
+    returns fp32 ``[B, V]`` (contiguous), to be handed to ``sample_logits`` / ``token_logprobs``.
+
+    ``tokens``: a flat int32 buffer ``[T]``; ``ranges``: int32 ``[B, 3]`` of ``(start, prompt_end,
+    end)`` with ``0 <= start <= prompt_end <= end <= T``: row ``b``'s prompt is
+    ``tokens[start:prompt_end]`` and its produced tokens are ``tokens[prompt_end:end]``. Ranges of
+    different rows may overlap (the rows of one sequence in a speculative verify round share a
+    region and differ in ``end``). Both may be host lists (checked here: a bad range or an id
+    outside ``[0, V)`` is a ``ValueError``; one packed upload) or tensors (used as given; the kernel
+    skips ids outside ``[0, V)`` and clamps ranges into the buffer). ``repetition`` (finite, > 0),
+    ``presence`` and ``frequency`` (finite) are each a scalar, a sequence of ``B`` or a tensor of ``B``.
+
+    Per row, with ``x`` the stored logit as fp32, ``seen_i`` "``i`` occurs in the history" and
+    ``c_i`` its count among the produced tokens, each step one IEEE fp32 operation:
+      1. ``y = x``; if ``seen_i``: ``y = x * inv_rep`` if ``x > 0`` else ``x * repetition``, with
+         ``inv_rep = fp32(1) / fp32(repetition)`` computed once on the host (prompt and output
+         count for repetition, as in HF transformers and vLLM);
+      2. ``y = y - fp32(frequency) * float(c_i)``;
+      3. if ``c_i > 0``: ``y = y - fp32(presence)``.
+    Tokens outside the history, and every token of a neutral row, come out as the exact fp32 image
+    of the stored logit. The result is a bitwise function of the row's inputs: the same as
+    ``reference.penalize_logits_ref`` on normal-range values.
+
+    The gfx950 kernel takes what ``sample_logits_supported`` takes and uses a zeroed int32
+    ``[B, V]`` workspace that it leaves zeroed; anything else runs the reference. ``B == 0``
+    returns an empty tensor without a launch."""
+    B, V = _check_logits(logits)
+    repetition = _per_row("repetition", repetition, B, float)
+    presence = _per_row("presence", presence, B, float)
+    frequency = _per_row("frequency", frequency, B, float)
+    check_penalty_params(repetition, presence, frequency)
+    import numpy as np
+
+    host = not torch.is_tensor(tokens) and not torch.is_tensor(ranges)
+    if host:
+        tok = np.asarray(tokens, dtype=np.int64).reshape(-1)
+        rng = np.asarray(ranges, dtype=np.int64).reshape(-1, 3)
+        T = tok.shape[0]
+        if rng.shape[0] != B:
+            raise ValueError(f"ranges has {rng.shape[0]} rows for {B} rows of logits")
+        if B and not ((0 <= rng[:, 0]) & (rng[:, 0] <= rng[:, 1]) & (rng[:, 1] <= rng[:, 2]) & (rng[:, 2] <= T)).all():
+            raise ValueError(f"ranges must hold 0 <= start <= prompt_end <= end <= {T}")
+        if T and V and not ((tok >= 0) & (tok < V)).all():
+            raise ValueError(f"tokens must lie in [0, {V})")
+    else:
+        if tuple(ranges.shape) != (B, 3):
+            raise ValueError(f"ranges must be [{B}, 3], got {tuple(ranges.shape)}")
+        T = tokens.numel()
+    if B == 0:
+        return torch.empty(0, V, dtype=torch.float32, device=logits.device)
+    if V < 1:
+        raise ValueError("logits must have at least one column")
+    if not sample_logits_supported(logits):
+        return ref.penalize_logits_ref(logits, tokens, ranges, repetition, presence, frequency)
+    dev = logits.device
+    rep32 = np.array(repetition, dtype=np.float32)
+    prm = np.stack([rep32, np.float32(1.0) / rep32, np.array(frequency, dtype=np.float32),
+                    np.array(presence, dtype=np.float32)], axis=1)
+    if host:  # parameters, ranges and tokens in one upload
+        packed = torch.from_numpy(np.concatenate([prm.view(np.int32).reshape(-1), rng.astype(np.int32).reshape(-1),
+                                                  tok.astype(np.int32)])).to(dev)
+        prm_t, rng_t, tok_t = packed[:4 * B], packed[4 * B: 7 * B], packed[7 * B:]
+    else:
+        prm_t = torch.from_numpy(prm).to(dev)
+        rng_t = ranges.to(device=dev, dtype=torch.int32).contiguous()
+        tok_t = tokens.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+    counts = _workspace(dev, "penalty_counts", B * V, torch.int32, zero=True)
+    out = torch.empty(B, V, dtype=torch.float32, device=dev)
+    check(lib().rca_penalize_logits(logits.data_ptr(), logits.stride(0), 1 if logits.dtype == torch.bfloat16 else 0,
+                                    tok_t.data_ptr() if T else None, rng_t.data_ptr(), prm_t.data_ptr(),
+                                    counts.data_ptr(), out.data_ptr(), B, V, T, stream_ptr(dev)),
+          "rca_penalize_logits")
+    return out
+
+
+def token_logprobs(logits, tokens, top_n=0):
+    """Log-probabilities of one step, in one launch: ``(lp fp32 [B], top_ids int64 [B, top_n],
+    top_lp fp32 [B, top_n])``.
+
+    ``tokens``: int64 ``[B]``, e.g. ``sample_logits``' output, used on the device as it is (no host
+    sync); ``top_n`` in ``0..20``. Per row, with ``x`` the stored logits, ``m = max x`` and
+    ``S = sum exp(x_i - m)``: ``lp_i = (x_i - m) - log S``, the log-softmax at temperature 1 and
+    before any top-k / top-p / min-p filter of exactly the tensor given (hand it what the sampler
+    was handed: the penalized logits when penalties are on). ``lp`` is ``lp_i`` at the row's token
+    (NaN for an id outside ``[0, V)``), ``top_ids`` the ``top_n`` largest logits in descending
+    order, equal logits by ascending index, ``top_lp`` their ``lp_i``; past ``V`` entries the tail
+    is ``-1`` / ``-inf``. ``S`` is summed in 2**-40 fixed point, so the outputs are bitwise
+    reproducible functions of the row.
+
+    The gfx950 kernel takes what ``sample_logits_supported`` takes; anything else runs
+    ``reference.token_logprobs_ref``. ``B == 0`` returns empty tensors without a launch."""
+    B, V = _check_logits(logits)
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= LOGPROBS_MAX_TOP:
+        raise ValueError(f"top_n must be an int in 0..{LOGPROBS_MAX_TOP}, got {top_n!r}")
+    if not torch.is_tensor(tokens) or tokens.dim() != 1 or tokens.shape[0] != B:
+        raise ValueError(f"tokens must be a tensor of {B} ids")
+    dev = logits.device
+    if B == 0:
+        return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, top_n, dtype=torch.int64, device=dev),
+                torch.empty(0, top_n, dtype=torch.float32, device=dev))
+    if V < 1:
+        raise ValueError("logits must have at least one column")
+    if not sample_logits_supported(logits):
+        return ref.token_logprobs_ref(logits, tokens, top_n)
+    tokens = tokens.to(device=dev, dtype=torch.int64).contiguous()
+    lp = torch.empty(B, dtype=torch.float32, device=dev)
+    top_ids = torch.empty(B, top_n, dtype=torch.int64, device=dev)
+    top_lp = torch.empty(B, top_n, dtype=torch.float32, device=dev)
+    check(lib().rca_token_logprobs(logits.data_ptr(), logits.stride(0), 1 if logits.dtype == torch.bfloat16 else 0,
+                                   tokens.data_ptr(), lp.data_ptr(), top_ids.data_ptr() if top_n else None,
+                                   top_lp.data_ptr() if top_n else None, B, V, top_n, stream_ptr(dev)),
+          "rca_token_logprobs")
+    return lp, top_ids, top_lp
 
 
 # ----------------------------------------------------------------------------------- FP8 weights

@@ -92,6 +92,8 @@ _SIGS = {
                                     + [c_float, c_int, c_void_p]),
     "rca_attn_extend_num_splits": (c_int, [c_int] * 6),
     "rca_sample_logits": (c_int, [c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "rca_penalize_logits": (c_int, [c_void_p, c_ll, c_int] + [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
+    "rca_token_logprobs": (c_int, [c_void_p, c_ll, c_int] + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
     "rca_linear_w8_splits": (c_int, [c_int, c_int]),
     "rca_linear_w8a16": (c_int, [c_void_p] * 5 + [c_ll, c_int, c_int, c_int, c_ll, c_ll, c_void_p]),
     "rca_dequant_w8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -425,3 +425,75 @@ def sample_logits_ref(logits, temperature, top_k, top_p, min_p, seeds, steps, un
         hit = torch.nonzero(keep & (run > u[b] * w.sum()))
         out[b] = int(hit[0]) if hit.numel() else int(torch.nonzero(keep)[-1])
     return out.to(logits.device)
+
+
+def _host_ints(values):
+    """``values`` (a sequence or a tensor of ints, any shape) as nested Python lists."""
+    return values.detach().cpu().tolist() if torch.is_tensor(values) else [
+        list(v) if isinstance(v, (list, tuple)) else v for v in values]
+
+
+def penalize_logits_ref(logits, tokens, ranges, repetition, presence, frequency):
+    """Reference of ``ops.penalize_logits``: fp32 ``[B, V]`` on ``logits.device``; every parameter
+    is a sequence (or tensor) of ``B`` values, taken at fp32 precision.
+
+    Row ``b`` has the history ``tokens[start:end]`` with ``(start, prompt_end, end) = ranges[b]``,
+    of which ``tokens[prompt_end:end]`` were produced; ids outside ``[0, V)`` are ignored. With
+    ``x`` the stored logit as fp32, ``seen_i`` "token ``i`` occurs in the history" and ``c_i`` its
+    number of occurrences among the produced tokens, each step one IEEE fp32 operation:
+      1. ``y = x``; if ``seen_i``: ``y = x * (fp32(1) / fp32(repetition))`` if ``x > 0`` else ``x * repetition``;
+      2. ``y = y - frequency * float(c_i)`` (the product rounded, then the difference);
+      3. if ``c_i > 0``: ``y = y - presence``.
+    A token outside the history keeps the exact fp32 image of its logit, and so does every token
+    of a row with neutral parameters (1, 0, 0)."""
+    B, V = logits.shape
+    x_all = logits.detach().float().cpu()
+    tokens = torch.as_tensor(_host_ints(tokens), dtype=torch.long).reshape(-1)
+    ranges = _host_ints(ranges)
+    repetition, presence, frequency = (v.detach().cpu().tolist() if torch.is_tensor(v) else list(v)
+                                       for v in (repetition, presence, frequency))
+    out = torch.empty(B, V, dtype=torch.float32)
+    one = torch.tensor(1.0, dtype=torch.float32)
+    for b in range(B):
+        start, prompt_end, end = (int(v) for v in ranges[b])
+        rep, pres, freq = (torch.tensor(float(v), dtype=torch.float32)
+                           for v in (repetition[b], presence[b], frequency[b]))
+        hist, made = tokens[start:end], tokens[prompt_end:end]
+        hist, made = hist[(hist >= 0) & (hist < V)], made[(made >= 0) & (made < V)]
+        seen = torch.zeros(V, dtype=torch.bool)
+        seen[hist] = True
+        c = torch.bincount(made, minlength=V)
+        x = x_all[b]
+        y = torch.where(seen, torch.where(x > 0, x * (one / rep), x * rep), x)
+        y = y - freq * c.float()
+        out[b] = torch.where(c > 0, y - pres, y)
+    return out.to(logits.device)
+
+
+def token_logprobs_ref(logits, tokens, top_n=0):
+    """Reference of ``ops.token_logprobs``: ``(lp fp32 [B], top_ids int64 [B, top_n], top_lp fp32
+    [B, top_n])`` on ``logits.device``.
+
+    Per row, with ``x`` the stored logits as fp32 and ``m = max x``: ``w_i = exp(x_i - m)`` in fp32,
+    ``S = sum w_i`` and everything after it in float64, ``lp_i = (x_i - m) - log S``, rounded to
+    fp32 at the end. ``lp`` is ``lp_i`` at the row's token; ``top_ids`` are the ``top_n`` largest
+    logits in descending order, equal logits by ascending index (a stable descending sort), and
+    ``top_lp`` their ``lp_i``. Past ``V`` entries the tail is ``-1`` / ``-inf``."""
+    B, V = logits.shape
+    top_n = int(top_n)
+    x = logits.detach().float().cpu()
+    tokens = torch.as_tensor(tokens).detach().cpu().long().reshape(-1)
+    top_ids = torch.full((B, top_n), -1, dtype=torch.int64)
+    top_lp = torch.full((B, top_n), float("-inf"), dtype=torch.float32)
+    if B == 0 or V == 0:
+        return torch.empty(B, dtype=torch.float32).to(logits.device), top_ids.to(logits.device), top_lp.to(logits.device)
+    m = x.max(dim=1, keepdim=True).values
+    d = x - m
+    lp_all = d.double() - torch.exp(d).double().sum(dim=1, keepdim=True).log()
+    lp = lp_all.gather(1, tokens[:, None])[:, 0].float()
+    n = min(top_n, V)
+    if n:
+        order = torch.sort(x, dim=1, descending=True, stable=True).indices[:, :n]
+        top_ids[:, :n] = order
+        top_lp[:, :n] = lp_all.gather(1, order).float()
+    return lp.to(logits.device), top_ids.to(logits.device), top_lp.to(logits.device)

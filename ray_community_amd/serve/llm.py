@@ -65,7 +65,7 @@ class _LlamaDeployment:
         self.default_max_new_tokens = int(default_max_new_tokens)
         # one model thread: the engine is not re-entrant, and per-thread GPU library state stays warm
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="llama-engine")
-        # request id -> (queue, max_new_tokens, tokens routed so far). Entries are added on the engine
+        # request id -> (queue, max_new_tokens, tokens routed so far, wants logprobs). Entries are added on the engine
         # thread (generate.add) and read / removed on the event loop: single dict operations, which the
         # GIL makes atomic, and an entry is complete before its request can produce a token.
         self._queues = {}
@@ -78,11 +78,19 @@ class _LlamaDeployment:
         try:
             while self._queues or self.engine.has_work():
                 events = await loop.run_in_executor(self._exec, self.engine.step)
+                lps = {}  # request id -> iterator over its new logprob entries, aligned with its events
                 for rid, tok, finished in events:
                     entry = self._queues.get(rid)
                     if entry is not None:
                         entry[2] += 1
+                        if entry[3]:
+                            if rid not in lps:
+                                lps[rid] = iter(self.engine.pop_logprobs(rid))
+                            _, lp, top = next(lps[rid])
+                            tok = {"token": tok, "logprob": lp, "top_logprobs": [[i, v] for i, v in top]}
                         entry[0].put_nowait((tok, finished))
+                    else:
+                        self.engine.pop_logprobs(rid)  # the consumer went away: nobody will ask for them
                 if not events and not self.engine.num_prefilling:
                     await asyncio.sleep(0.001)  # everything is waiting for cache blocks
         except BaseException as e:  # a failed step fails every open stream instead of hanging it
@@ -93,10 +101,14 @@ class _LlamaDeployment:
             self._driver = None
 
     async def generate(self, prompt_tokens, max_new_tokens=None, temperature: float = 0.0, top_k: int = 0,
-                       eos_token_id=None, seed=None, top_p: float = 1.0, min_p: float = 0.0, adapter=None):
+                       eos_token_id=None, seed=None, top_p: float = 1.0, min_p: float = 0.0, adapter=None,
+                       repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                       frequency_penalty: float = 0.0, logprobs=None):
         """Async generator of the new token ids of one request (sampling arguments as in
         ``GenerationEngine.add_request``). ``adapter``: the name of a loaded LoRA adapter; without
-        one, a non-empty ``serve.get_multiplexed_model_id()`` of the request is the name."""
+        one, a non-empty ``serve.get_multiplexed_model_id()`` of the request is the name. With
+        ``logprobs`` (``0..20`` alternatives) every item is ``{"token": id, "logprob": lp,
+        "top_logprobs": [[id, lp], ...]}`` instead of a bare id."""
         from .multiplex import get_multiplexed_model_id
 
         if adapter is None and self.lora is not None:
@@ -108,8 +120,10 @@ class _LlamaDeployment:
         def add():  # on the engine thread, so no step can run between queueing and registering
             rid = self.engine.add_request(list(prompt_tokens), n, temperature=temperature, top_k=top_k,
                                           eos_token_id=eos_token_id, seed=seed, top_p=top_p, min_p=min_p,
+                                          repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                          frequency_penalty=frequency_penalty, logprobs=logprobs,
                                           **({} if adapter is None else {"adapter": adapter}))
-            self._queues[rid] = [q, n, 0]
+            self._queues[rid] = [q, n, 0, logprobs is not None]
             return rid
 
         rid = await loop.run_in_executor(self._exec, add)
@@ -176,15 +190,18 @@ class _LlamaDeployment:
 
     async def __call__(self, request):
         """HTTP: JSON body ``{"prompt_tokens": [...], "max_new_tokens": n}`` (optionally
-        ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``eos_token_id``, ``seed``, ``adapter``) -> newline-delimited token ids."""
+        ``temperature``, ``top_k``, ``top_p``, ``min_p``, ``eos_token_id``, ``seed``, ``adapter``,
+        ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``, ``logprobs``) -> newline-delimited
+        token ids, or with ``logprobs`` one JSON object ``{"token", "logprob", "top_logprobs"}`` per line."""
         body = json.loads(await request.body())
         kw = {k: body[k] for k in ("max_new_tokens", "temperature", "top_k", "top_p", "min_p", "eos_token_id", "seed",
-                                          "adapter")
+                                          "adapter", "repetition_penalty", "presence_penalty", "frequency_penalty",
+                                          "logprobs")
               if k in body}
 
         async def lines():
             async for tok in self.generate(body["prompt_tokens"], **kw):
-                yield f"{tok}\n"
+                yield f"{json.dumps(tok) if isinstance(tok, dict) else tok}\n"
 
         return lines()
 

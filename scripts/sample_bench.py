@@ -14,6 +14,13 @@ One more row times the kernel of (c) alone with device events and states it as a
 read of the logits at ``--stream-tbs`` (the project's measured stream rate, 6.5 TB/s).
 End to end: tokens/s of a llama3-1b engine with 32 sampled slots, ``fused_sampling`` off and on,
 alternating in one process. Prints one JSON line per measurement; a run without a GPU fails.
+
+``--penalties`` and / or ``--logprobs N`` run these arms instead (``profiles/sampling_penalties.md``):
+``ops.penalize_logits`` and ``ops.token_logprobs`` at B = 32, V = 128256, bf16, 4096 tokens of history
+per row (1024 prompt + 3072 produced): the call as the decode round makes it (host lists: checks,
+packing, one upload, launch; ended by a synchronise), the same call on device tensors, and the
+kernel alone by device events; then llama3-1b ``generate`` tokens/s, 32 prompts of 512 tokens,
+with and without them against the plain ``fused_sampling`` arm, alternating in one process.
 """
 import argparse
 import json
@@ -133,6 +140,96 @@ def bench_engine(rounds, slots=32, new_tokens=32):
     return out
 
 
+def bench_penalty_ops(rounds, penalties, logprobs, B=32, hist=4096, prompt=1024):
+    import numpy as np
+
+    from ray_community_amd.ops._lib import lib, stream_ptr
+
+    g = torch.Generator(device="cuda").manual_seed(1)
+    logits = (torch.randn(B, V, device="cuda", generator=g) * 4).bfloat16()
+    flat = torch.randint(0, V, (B * hist,), generator=torch.Generator().manual_seed(2)).tolist()
+    ranges = [(b * hist, b * hist + prompt, (b + 1) * hist) for b in range(B)]
+    tok_dev = torch.tensor(flat, dtype=torch.int32, device="cuda")
+    rng_dev = torch.tensor(ranges, dtype=torch.int32, device="cuda")
+    picked = ops.sample_logits(logits, T, K, P, 0.0, seeds=1, steps=0)
+    L, st = lib(), stream_ptr(logits.device)
+    arms, kernels = {}, {}
+    if penalties:
+        arms["penalize_logits_host_lists"] = lambda: ops.penalize_logits(logits, flat, ranges, 1.3, 0.4, 0.25)
+        arms["penalize_logits_device_tensors"] = lambda: ops.penalize_logits(logits, tok_dev, rng_dev, 1.3, 0.4, 0.25)
+        prm = torch.tensor([[1.3, 1 / 1.3, 0.25, 0.4]] * B, dtype=torch.float32, device="cuda")
+        counts = torch.zeros(B * V, dtype=torch.int32, device="cuda")
+        image = torch.empty(B, V, dtype=torch.float32, device="cuda")
+        kernels["penalize_logits_kernel_ms"] = lambda: L.rca_penalize_logits(
+            logits.data_ptr(), logits.stride(0), 1, tok_dev.data_ptr(), rng_dev.data_ptr(), prm.data_ptr(),
+            counts.data_ptr(), image.data_ptr(), B, V, B * hist, st)
+    if logprobs is not None:
+        arms["token_logprobs"] = lambda: ops.token_logprobs(logits, picked, logprobs)
+        lp = torch.empty(B, dtype=torch.float32, device="cuda")
+        ids = torch.empty(B, max(logprobs, 1), dtype=torch.int64, device="cuda")
+        tlp = torch.empty(B, max(logprobs, 1), dtype=torch.float32, device="cuda")
+        kernels["token_logprobs_kernel_ms"] = lambda: L.rca_token_logprobs(
+            logits.data_ptr(), logits.stride(0), 1, picked.data_ptr(), lp.data_ptr(), ids.data_ptr(), tlp.data_ptr(),
+            B, V, logprobs, st)
+    for fn in list(arms.values()) + list(kernels.values()):
+        for _ in range(3):
+            fn()
+    ms = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, fn in arms.items():
+            ms[name].append(_timed(fn))
+    out = {"B": B, "V": V, "dtype": "bf16", "history": hist, "logprobs": logprobs, "rounds": rounds,
+           "call_ms": {k: _stat(v) for k, v in ms.items()}}
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for name, fn in kernels.items():
+        kern, reps = [], 20
+        for _ in range(rounds):
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(reps):
+                fn()
+            stop.record()
+            torch.cuda.synchronize()
+            kern.append(start.elapsed_time(stop) / reps)
+        out[name] = _stat(kern)
+    return out
+
+
+def bench_penalty_generate(rounds, penalties, logprobs, batch=32, prompt_len=512, new_tokens=32):
+    torch.manual_seed(0)
+    model = build_llama("llama3-1b", device="cuda", dtype=torch.bfloat16).eval()
+    g = torch.Generator().manual_seed(2)
+    prompts = [torch.randint(0, model.cfg.vocab_size, (prompt_len,), generator=g).tolist() for _ in range(batch)]
+    pen = dict(repetition_penalty=1.3, presence_penalty=0.4, frequency_penalty=0.25)
+    arms = {"plain_fused": {}}
+    if penalties:
+        arms["penalties"] = pen
+    if logprobs is not None:
+        arms["logprobs"] = {"logprobs": logprobs}
+    if penalties and logprobs is not None:
+        arms["penalties_and_logprobs"] = dict(pen, logprobs=logprobs)
+
+    def run(kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model.generate(prompts, new_tokens, temperature=T, top_k=K, seed=1, fused_sampling=True, **kw)
+        torch.cuda.synchronize()
+        toks = out[0] if "logprobs" in kw else out
+        return sum(len(t) for t in toks) / (time.perf_counter() - t0)
+
+    for kw in arms.values():
+        run(kw)
+    tps = {name: [] for name in arms}
+    for _ in range(rounds):
+        for name, kw in arms.items():
+            tps[name].append(run(kw))
+    out = {"generate": "llama3-1b", "batch": batch, "prompt_len": prompt_len, "new_tokens": new_tokens,
+           "rounds": rounds, "tokens_per_s": {k: _stat(v) for k, v in tps.items()}}
+    base = out["tokens_per_s"]["plain_fused"]["median"]
+    out["over_plain"] = {k: v["median"] / base for k, v in out["tokens_per_s"].items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
@@ -140,10 +237,22 @@ def main():
     ap.add_argument("--skip-engine", action="store_true")
     ap.add_argument("--stream-tbs", type=float, default=6.5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--penalties", action="store_true", help="the ops.penalize_logits arms instead of the sampler's")
+    ap.add_argument("--logprobs", type=int, default=None, metavar="N", help="the ops.token_logprobs arms (N alternatives)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_bench needs a GPU: nothing here can be measured without one")
     results = []
+    if a.penalties or a.logprobs is not None:
+        results.append(bench_penalty_ops(a.rounds, a.penalties, a.logprobs))
+        print(json.dumps(results[-1]), flush=True)
+        if not a.skip_engine:
+            results.append(bench_penalty_generate(a.engine_rounds, a.penalties, a.logprobs))
+            print(json.dumps(results[-1]), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(results, f, indent=1)
+        return
     for B in (1, 32, 256):
         results.append(bench_arms(B, a.rounds, a.stream_tbs))
         print(json.dumps(results[-1]), flush=True)
