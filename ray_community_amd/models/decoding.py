@@ -196,7 +196,7 @@ def sample_rows(logits, picks):
     return toks
 
 
-def decode_round(model, cache, slots, proposer, num_draft, stats, sample=sample_rows):
+def decode_round(model, cache, slots, proposer, num_draft, stats, sample=sample_rows, *, runner=None):
     """One decode round over ``slots`` (a ``Stream`` or ``None`` per position); returns ``(slot,
     tokens, finished)`` for every live slot, in slot order, with the streams advanced. What
     finished is the caller's to free.
@@ -212,7 +212,12 @@ def decode_round(model, cache, slots, proposer, num_draft, stats, sample=sample_
     engine: reserved) for; the extend cannot run out of blocks.
 
     If some live stream has a LoRA ``adapter``, both calls carry ``adapters=[...]`` (one per row of
-    ``decode_step``, one per sequence of ``extend``); otherwise the keyword is not passed at all."""
+    ``decode_step``, one per sequence of ``extend``); otherwise the keyword is not passed at all.
+
+    ``runner`` (a ``models.decode_graph.DecodeRunner`` over ``model``, ``cache`` and ``len(slots)``
+    rows; ``graph_decode=True`` of the callers): its ``step`` takes the place of ``decode_step``. It
+    runs a LoRA round through ``decode_step`` itself, and a verify round goes through ``extend`` as
+    ever; the runner counts both as eager fallbacks."""
     live = [s for s, st in enumerate(slots) if st is not None]
     if not live:
         return []
@@ -221,12 +226,18 @@ def decode_round(model, cache, slots, proposer, num_draft, stats, sample=sample_
     lora = any(slots[s].adapter is not None for s in live)
     if not any(drafts):
         akw = {"adapters": [st.adapter if st is not None else None for st in slots]} if lora else {}
-        logits = model.decode_step([st.history[-1] if st is not None else 0 for st in slots], cache,
-                                   [st.seq_id if st is not None else None for st in slots], **akw)
+        toks_in = [st.history[-1] if st is not None else 0 for st in slots]
+        ids = [st.seq_id if st is not None else None for st in slots]
+        if runner is not None:
+            logits = runner.step(toks_in, ids, **akw)
+        else:
+            logits = model.decode_step(toks_in, cache, ids, **akw)
         toks = sample(logits, [(slots[s], s) for s in live])
         return [(s, [tok], slots[s].advance([tok])) for s, tok in zip(live, toks)]
     rows = [[slots[s].history[-1]] + draft for s, draft in zip(live, drafts)]
     akw = {"adapters": [slots[s].adapter for s in live]} if lora else {}
+    if runner is not None:
+        runner.count_fallback()
     logits = model.extend(rows, cache, [slots[s].seq_id for s in live], all_logits=True, num_splits=None, **akw)
     sampled, entries = _sample_fused(logits, [(slots[s], slots[s].produced + j, row[1: 1 + j])
                                               for s, row in zip(live, rows) for j in range(len(row))])

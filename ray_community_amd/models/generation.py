@@ -64,7 +64,7 @@ class GenerationEngine:
     def __init__(self, model, cache: Optional[PagedKVCache] = None, max_slots: int = 8,
                  num_blocks: Optional[int] = None, page_size: int = 16, prefill_chunk: Optional[int] = None,
                  fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
-                 cache_bytes: Optional[int] = None):
+                 cache_bytes: Optional[int] = None, graph_decode: bool = False):
         """``speculative``: ``None``, a number of draft tokens per step (prompt lookup,
         ``NgramProposer``) or a proposer object; it implies ``fused_sampling``, since a draft is
         verified by re-drawing its token with ``ops.sample_logits``.
@@ -76,7 +76,12 @@ class GenerationEngine:
         attends over the fresh, unquantised K/V while ``extend`` and ``decode_step`` read the
         quantised cache, so a ``prefill_chunk`` stream may differ from the unchunked one;
         speculative decoding keeps its guarantee, since the verify ``extend`` and ``decode_step``
-        read the same quantised bytes."""
+        read the same quantised bytes.
+
+        ``graph_decode=True`` runs the decode step of every round through a ``DecodeRunner`` over the
+        engine's cache and ``max_slots`` rows (``models/decode_graph.py``: static buffers, one
+        captured HIP graph per block-table bucket; the uncaptured body when the model is not on a
+        GPU). ``self.runner.stats`` counts graphs, replays and the rounds that ran eagerly."""
         if num_blocks is not None and cache_bytes is not None:
             raise ValueError("give num_blocks or cache_bytes, not both")
         if prefill_chunk is not None and int(prefill_chunk) < 1:
@@ -100,6 +105,12 @@ class GenerationEngine:
         self.slots: List[Optional[_Request]] = [None] * int(max_slots)
         self.waiting = deque()
         self._ids = itertools.count()
+        self.runner = None
+        if graph_decode:
+            from .decode_graph import DecodeRunner
+
+            self.runner = DecodeRunner(model, cache, len(self.slots))
+        self._round_kw = {} if self.runner is None else {"runner": self.runner}
 
     # -------------------------------------------------------------------------------- requests
     def _check_adapter(self, adapter):
@@ -373,7 +384,7 @@ class GenerationEngine:
         ``extend`` in this step (``joined``), ride along as inactive slots."""
         live = [r if r is not None and not r.prefilling and r.rid not in joined else None for r in self.slots]
         for slot, toks, finished in decode_round(self.model, self.cache, live, self._proposer, self.num_draft,
-                                                 self.spec_stats):
+                                                 self.spec_stats, **self._round_kw):
             self._emit(slot, toks, finished, events)
 
     def step(self) -> List[Tuple[int, int, bool]]:

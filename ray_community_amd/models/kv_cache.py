@@ -173,6 +173,16 @@ class PagedKVCache:
         table = [r + [0] * (width - len(r)) for r in rows]
         return torch.tensor(table, dtype=torch.int32).reshape(len(rows), width).to(self.device)
 
+    def fill_decode_inputs(self, seq_ids: Sequence[Optional[Hashable]], context_lens, block_table) -> None:
+        """``context_lens(seq_ids)`` and ``block_table(seq_ids)`` written into host arrays the caller
+        owns (numpy ``[B]`` and ``[B, W]``, e.g. views of a pinned staging tensor) instead of new device
+        tensors; ``W`` must hold the longest block list, and the rest of a row is zeroed."""
+        for b, s in enumerate(seq_ids):
+            blocks = self._blocks.get(s, ()) if s is not None else ()
+            context_lens[b] = self._lens.get(s, 0) if s is not None else 0
+            block_table[b, :len(blocks)] = blocks
+            block_table[b, len(blocks):] = 0
+
     def context_lens(self, seq_ids: Sequence[Optional[Hashable]]) -> torch.Tensor:
         """int32 ``[len(seq_ids)]``: tokens held per sequence (0 for ``None`` / unknown ids)."""
         lens = [self._lens.get(s, 0) if s is not None else 0 for s in seq_ids]

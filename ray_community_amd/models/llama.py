@@ -153,6 +153,9 @@ class Llama(nn.Module):
         self.norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
         self.lm_head = None if cfg.tie_embeddings else FusedWgradLinear(cfg.hidden_size, cfg.vocab_size)
         self._cs = {}
+        # bumped by whatever replaces a module or moves the parameters: a captured decode graph
+        # (models/decode_graph.py) holds their addresses and is dropped when this changes
+        self.module_epoch = 0
         self.reset_parameters()
 
     @torch.no_grad()
@@ -171,6 +174,7 @@ class Llama(nn.Module):
         """Quantise the linears' weights in place for inference (``models/quant.py``): ``"fp8"``
         halves their bytes; ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run
         ``ops.linear_w8``. Idempotent. Training paths are not available afterwards."""
+        self.module_epoch += 1
         return quantize_weights_(self, dtype)
 
     def enable_lora_(self, max_adapters: int, max_rank: int):
@@ -179,7 +183,12 @@ class Llama(nn.Module):
         ``LoraLinear``s around their base modules (before or after ``quantize_weights_``), and
         ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` take ``adapters=``. With no adapter
         named every logit keeps its bits. Training paths are not available afterwards."""
+        self.module_epoch += 1
         return _lora.enable_lora_(self, max_adapters, max_rank)
+
+    def _apply(self, fn, recurse=True):
+        self.module_epoch += 1  # ``.to(device)`` and its kin give the parameters new storage
+        return super()._apply(fn, recurse)
 
     def load_adapter(self, name, adapter):
         """Copy a ``LoraAdapter`` into a free slot under ``name``. ``AdapterSlotsFull`` when there is
@@ -403,7 +412,7 @@ class Llama(nn.Module):
                  seed=None, cache=None, prefill_chunk=None, top_p: float = 1.0, min_p: float = 0.0,
                  fused_sampling: bool = False, speculative=None, kv_cache_dtype=None, adapters=None,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                 logprobs=None):
+                 logprobs=None, graph_decode: bool = False):
         """Generate up to ``max_new_tokens`` tokens after each prompt (a list of token-id lists);
         returns the new tokens per prompt. Greedy at ``temperature == 0``, otherwise sampled
         (optionally from the ``top_k`` logits) with a generator seeded by ``seed``. A sequence
@@ -440,7 +449,13 @@ class Llama(nn.Module):
         the number ``0..20`` of alternatives to record per produced token; the call then returns
         ``(tokens, logprobs)`` with one ``(token, logprob, [(id, logprob), ...])`` entry per token
         (``ops.token_logprobs``: temperature 1, before top-k / top-p / min-p, after the penalties).
-        A non-neutral penalty or ``logprobs`` selects the batched sampler like ``fused_sampling``."""
+        A non-neutral penalty or ``logprobs`` selects the batched sampler like ``fused_sampling``.
+
+        ``graph_decode=True`` runs the decode steps through a ``DecodeRunner``
+        (``models/decode_graph.py``): static input buffers and one captured HIP graph per block-table
+        bucket, replayed per step; the same body uncaptured when the model is not on a GPU. LoRA
+        rounds and speculative verify rounds run as without it. A runner belongs to a cache, so pass
+        ``cache=`` to keep its graphs from one call to the next."""
         from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows, sample_tokens
         from .kv_cache import PagedKVCache
         from .speculative import new_stats, resolve_speculative
@@ -483,6 +498,11 @@ class Llama(nn.Module):
         stats = new_stats()
         if proposer is not None:
             self.spec_stats = stats
+        rkw = {}
+        if graph_decode:
+            from .decode_graph import runner_for
+
+            rkw["runner"] = runner_for(self, cache, len(prompts))
 
         def settle(emitted):
             for b, _, finished in emitted:
@@ -498,7 +518,7 @@ class Llama(nn.Module):
             first = sample(logits, [(st, b) for b, st in enumerate(streams)])
             settle([(b, [tok], st.advance([tok])) for b, (st, tok) in enumerate(zip(streams, first))])
             while any(st is not None for st in slots):
-                settle(decode_round(self, cache, slots, proposer, num_draft, stats, sample))
+                settle(decode_round(self, cache, slots, proposer, num_draft, stats, sample, **rkw))
         finally:
             for sid in ids:
                 cache.free(sid)

@@ -39,6 +39,7 @@ __all__ = [
     "paged_decode_supported",
     "paged_kv_fp8_supported",
     "kv_cache_append_",
+    "rope_kv_append_decode_",
     "paged_attention_decode",
     "paged_attention_extend",
     "paged_extend_num_splits",
@@ -1158,6 +1159,63 @@ def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: i
                                         stream_ptr(qkv.device)), "rca_kv_cache_append")
         return
     ref.kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D, k_scale, v_scale)
+
+
+def rope_kv_append_decode_(qkv, cs, k_cache, v_cache, block_table, context_lens, Hq: int, Hk: int, D: int,
+                           k_scale=None, v_scale=None):
+    """The RoPE and the cache append of a decode step in one call, with nothing computed on the host:
+    ``apply_rope_`` and ``kv_cache_append_`` on positions and slots taken from ``block_table`` (int32
+    ``[B, max_blocks]``) and ``context_lens`` (int32 ``[B]``: each sequence's length *including* the
+    token of row ``b`` of the fused ``qkv`` ``[B, (Hq+2Hk)*D]``). In place; returns ``qkv``.
+
+    Row ``b`` with ``n = context_lens[b]`` has position ``n - 1`` and slot
+    ``block_table[b, (n-1) // page] * page + (n-1) % page``. It is inactive (left as it is, nothing
+    cached) if ``n <= 0``, if ``n`` exceeds ``max_blocks * page`` or the rows of ``cs``, or if the
+    table entry is no block of the cache.
+
+    On the kernel path (``paged_decode_supported`` shapes, ``kv_cache_append_``'s alignment) this is
+    one launch whose result is bit for bit the two ops' (``ops/csrc/decode_step.hip``); anything
+    else, CPU tensors included, runs the two ops on positions and slots computed with torch ops."""
+    _check_paged_caches(k_cache, v_cache, Hk, D, k_scale, v_scale)
+    fp8 = k_scale is not None
+    W = (Hq + 2 * Hk) * D
+    if qkv.dim() != 2 or qkv.shape[1] != W or qkv.stride(1) != 1:
+        raise ValueError(f"qkv must be [B, {W}] with unit inner stride, got {tuple(qkv.shape)}")
+    _check_q_dtype("qkv", qkv, k_cache, fp8)
+    B = qkv.shape[0]
+    if block_table.dim() != 2 or block_table.shape[1] < 1:
+        raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(block_table.shape)}")
+    if context_lens.dim() != 1:
+        raise ValueError(f"context_lens must be 1-D, got shape {tuple(context_lens.shape)}")
+    _check_index("block_table", block_table, B, qkv.device)
+    _check_index("context_lens", context_lens, B, qkv.device)
+    if cs.dim() != 3 or tuple(cs.shape[1:]) != (D // 2, 2) or cs.device != qkv.device:
+        raise ValueError(f"cs must be [max_pos, {D // 2}, 2] on qkv's device, got {tuple(cs.shape)} on {cs.device}")
+    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
+    max_blocks = block_table.shape[1]
+    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
+            and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0 and cs.dtype == torch.float32
+            and cs.is_contiguous() and cs.data_ptr() % 16 == 0 and B * (Hq + 2 * Hk) * (D // 16) < 2 ** 31):
+        args = (qkv.data_ptr(), qkv.stride(0), cs.data_ptr(), min(cs.shape[0], 2 ** 31 - 1), block_table.data_ptr(),
+                context_lens.data_ptr(), max_blocks, k_cache.data_ptr(), v_cache.data_ptr())
+        dims = (B, Hq, Hk, D, page, num_blocks, stream_ptr(qkv.device))
+        if fp8:
+            check(lib().rca_rope_kv_append_decode_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr(), *dims),
+                  "rca_rope_kv_append_decode_fp8")
+        else:
+            check(lib().rca_rope_kv_append_decode(*args, *dims), "rca_rope_kv_append_decode")
+        return qkv
+    n = context_lens.long()
+    active = (n >= 1) & (n <= max_blocks * page) & (n <= cs.shape[0])
+    pos = torch.where(active, n - 1, torch.zeros_like(n))
+    blk = block_table.long().gather(1, (pos // page)[:, None]).squeeze(1)
+    active = active & (blk >= 0) & (blk < num_blocks)
+    pos = torch.where(active, pos, torch.zeros_like(pos))
+    slots = torch.where(active, blk * page + pos % page, torch.full_like(pos, -1)).to(torch.int32)
+    rot = apply_rope_(qkv.clone(), cs, 1, Hq, Hk, D, pos.to(torch.int32))
+    qkv.copy_(torch.where(active[:, None], rot, qkv))  # an inactive row keeps its bits, a -0.0 included
+    kv_cache_append_(k_cache, v_cache, qkv, slots, Hq, Hk, D, k_scale=k_scale, v_scale=v_scale)
+    return qkv
 
 
 def _check_paged_attention(letter, q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, k_scale=None,

@@ -100,6 +100,10 @@ _SIGS = {
     "rca_lora_splits": (c_int, [c_int, c_int]),
     "rca_lora_add": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_int, c_void_p, c_ll] + [c_int] * 5
                      + [c_void_p]),
+    "rca_rope_kv_append_decode": (c_int, [c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+                                  + [c_int] * 6 + [c_void_p]),
+    "rca_rope_kv_append_decode_fp8": (c_int, [c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4
+                                      + [c_int] * 6 + [c_void_p]),
 }
 
 

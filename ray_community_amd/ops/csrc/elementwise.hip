@@ -4,6 +4,7 @@
 // All accesses are 16 B per lane (8 x bf16). Grids are capped at 256 CUs x 8 blocks and
 // grid-stride the remainder (cdna_hip_programming.md Guideline 11).
 #include "common.h"
+#include "rope_rotate.h"
 #include <stdlib.h>
 
 static inline int grid_for(long long nvec, int block) {
@@ -171,16 +172,7 @@ __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, con
     float a[8], b[8], oa[8], ob[8];
     unpack8(*lo, a);
     unpack8(*hi, b);
-    const float4* csr = reinterpret_cast<const float4*>(cs + (long long)p * half + c);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 q = csr[j];  // (cos_j0, sin_j0, cos_j1, sin_j1)
-      const float c0 = q.x, s0 = sign * q.y, c1 = q.z, s1 = sign * q.w;
-      oa[2 * j] = a[2 * j] * c0 - b[2 * j] * s0;
-      ob[2 * j] = b[2 * j] * c0 + a[2 * j] * s0;
-      oa[2 * j + 1] = a[2 * j + 1] * c1 - b[2 * j + 1] * s1;
-      ob[2 * j + 1] = b[2 * j + 1] * c1 + a[2 * j + 1] * s1;
-    }
+    rope_rotate8(a, b, reinterpret_cast<const float4*>(cs + (long long)p * half + c), sign, oa, ob);
     *lo = pack8(oa);
     *hi = pack8(ob);
   }

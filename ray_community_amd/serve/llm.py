@@ -22,7 +22,7 @@ class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
                  num_blocks=None, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
                  prefill_chunk=None, fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
-                 cache_bytes=None, weight_dtype=None, lora=None, adapters=None):
+                 cache_bytes=None, weight_dtype=None, lora=None, adapters=None, graph_decode: bool = False):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
         ``torch.save``d state dict (without one the weights are initialised from ``seed``);
         ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
@@ -37,7 +37,9 @@ class _LlamaDeployment:
         the linears' weights once the state dict is loaded (``Llama.quantize_weights_``: half the
         weight bytes, activations stay in ``dtype``); ``lora={"max_adapters": n, "max_rank": r}``
         makes room for LoRA adapters (``Llama.enable_lora_``, after the quantisation) that requests
-        select by name, and ``adapters={"name": path}`` preloads ``LoraAdapter.save``d files."""
+        select by name, and ``adapters={"name": path}`` preloads ``LoraAdapter.save``d files;
+        ``graph_decode``: the engine replays its decode step as a captured HIP graph
+        (``GenerationEngine(graph_decode=True)``; on a CPU model the same step runs uncaptured)."""
         import torch
 
         from ..models import GenerationEngine, LoraAdapter, build_llama, weight_bytes
@@ -61,7 +63,7 @@ class _LlamaDeployment:
         self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
                                        prefill_chunk=prefill_chunk, fused_sampling=fused_sampling,
                                        speculative=speculative, kv_cache_dtype=kv_cache_dtype,
-                                       cache_bytes=cache_bytes)
+                                       cache_bytes=cache_bytes, **({"graph_decode": True} if graph_decode else {}))
         self.default_max_new_tokens = int(default_max_new_tokens)
         # one model thread: the engine is not re-entrant, and per-thread GPU library state stays warm
         self._exec = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="llama-engine")
@@ -166,7 +168,8 @@ class _LlamaDeployment:
         ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``, one with an fp8
         cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``, one with fp8
         weights adds ``"weight_dtype": "fp8"`` and ``"weight_bytes"`` (the model's parameters and buffers),
-        one with ``lora`` adds ``"lora": {"max_adapters", "max_rank", "loaded": [...], "bank_bytes"}``."""
+        one with ``lora`` adds ``"lora": {"max_adapters", "max_rank", "loaded": [...], "bank_bytes"}``,
+        one with ``graph_decode`` adds ``"graph_decode": {"graphs", "replays", "eager_warm", "eager_fallback"}``."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
                    for rid, e in list(self._queues.items())]
         st = {"active": self.engine.num_active, "waiting": len(self.engine.waiting), "streams": streams,
@@ -186,6 +189,8 @@ class _LlamaDeployment:
             from ..models.lora import bank_bytes
 
             st.update(lora={**self.lora, "loaded": self.model.loaded_adapters(), "bank_bytes": bank_bytes(self.model)})
+        if self.engine.runner is not None:
+            st.update(graph_decode=dict(self.engine.runner.stats))
         return st
 
     async def __call__(self, request):
