@@ -1123,6 +1123,15 @@ def _check_index(name, t, rows, device):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _check_fused_qkv(letter, qkv, k_cache, Hq, Hk, D, fp8):
+    """The fused ``qkv`` ``[letter, (Hq+2Hk)*D]`` of the append ops; returns its number of rows."""
+    W = (Hq + 2 * Hk) * D
+    if qkv.dim() != 2 or qkv.shape[1] != W or qkv.stride(1) != 1:
+        raise ValueError(f"qkv must be [{letter}, {W}] with unit inner stride, got {tuple(qkv.shape)}")
+    _check_q_dtype("qkv", qkv, k_cache, fp8)
+    return qkv.shape[0]
+
+
 def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: int, k_scale=None, v_scale=None):
     """Write the K and V heads of every token of the fused, already rotated ``qkv``
     ``[T, (Hq+2Hk)*D]`` into the paged caches ``[num_blocks, page_size, Hk, D]``, in place.
@@ -1136,27 +1145,15 @@ def kv_cache_append_(k_cache, v_cache, qkv, slot_mapping, Hq: int, Hk: int, D: i
     (``reference.kv_quantize_fp8_ref``); ``qkv`` is bf16 on the kernel path, any float dtype on
     the reference path."""
     _check_paged_caches(k_cache, v_cache, Hk, D, k_scale, v_scale)
-    fp8 = k_scale is not None
-    W = (Hq + 2 * Hk) * D
-    if qkv.dim() != 2 or qkv.shape[1] != W or qkv.stride(1) != 1:
-        raise ValueError(f"qkv must be [T, {W}] with unit inner stride, got {tuple(qkv.shape)}")
-    _check_q_dtype("qkv", qkv, k_cache, fp8)
-    T = qkv.shape[0]
+    T = _check_fused_qkv("T", qkv, k_cache, Hq, Hk, D, k_scale is not None)
     if slot_mapping.dim() != 1:
         raise ValueError(f"slot_mapping must be 1-D, got shape {tuple(slot_mapping.shape)}")
     _check_index("slot_mapping", slot_mapping, T, qkv.device)
-    page = k_cache.shape[1]
-    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
-            and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0):
-        if fp8:
-            check(lib().rca_kv_cache_append_fp8(qkv.data_ptr(), qkv.stride(0), slot_mapping.data_ptr(),
-                                                k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
-                                                v_scale.data_ptr(), T, Hq, Hk, D, k_cache.shape[0] * page,
-                                                stream_ptr(qkv.device)), "rca_kv_cache_append_fp8")
-            return
+    if _paged_kernel_ok(qkv, k_cache, Hq, Hk, D):
         check(lib().rca_kv_cache_append(qkv.data_ptr(), qkv.stride(0), slot_mapping.data_ptr(), k_cache.data_ptr(),
-                                        v_cache.data_ptr(), T, Hq, Hk, D, k_cache.shape[0] * page,
-                                        stream_ptr(qkv.device)), "rca_kv_cache_append")
+                                        v_cache.data_ptr(), _p(k_scale), _p(v_scale), T, Hq, Hk, D,
+                                        k_cache.shape[0] * k_cache.shape[1], stream_ptr(qkv.device)),
+              "rca_kv_cache_append")
         return
     ref.kv_cache_append_ref(k_cache, v_cache, qkv, slot_mapping, Hq, Hk, D, k_scale, v_scale)
 
@@ -1177,12 +1174,7 @@ def rope_kv_append_decode_(qkv, cs, k_cache, v_cache, block_table, context_lens,
     one launch whose result is bit for bit the two ops' (``ops/csrc/decode_step.hip``); anything
     else, CPU tensors included, runs the two ops on positions and slots computed with torch ops."""
     _check_paged_caches(k_cache, v_cache, Hk, D, k_scale, v_scale)
-    fp8 = k_scale is not None
-    W = (Hq + 2 * Hk) * D
-    if qkv.dim() != 2 or qkv.shape[1] != W or qkv.stride(1) != 1:
-        raise ValueError(f"qkv must be [B, {W}] with unit inner stride, got {tuple(qkv.shape)}")
-    _check_q_dtype("qkv", qkv, k_cache, fp8)
-    B = qkv.shape[0]
+    B = _check_fused_qkv("B", qkv, k_cache, Hq, Hk, D, k_scale is not None)
     if block_table.dim() != 2 or block_table.shape[1] < 1:
         raise ValueError(f"block_table must be [B, max_blocks >= 1], got {tuple(block_table.shape)}")
     if context_lens.dim() != 1:
@@ -1193,17 +1185,13 @@ def rope_kv_append_decode_(qkv, cs, k_cache, v_cache, block_table, context_lens,
         raise ValueError(f"cs must be [max_pos, {D // 2}, 2] on qkv's device, got {tuple(cs.shape)} on {cs.device}")
     num_blocks, page = k_cache.shape[0], k_cache.shape[1]
     max_blocks = block_table.shape[1]
-    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
-            and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0 and cs.dtype == torch.float32
-            and cs.is_contiguous() and cs.data_ptr() % 16 == 0 and B * (Hq + 2 * Hk) * (D // 16) < 2 ** 31):
-        args = (qkv.data_ptr(), qkv.stride(0), cs.data_ptr(), min(cs.shape[0], 2 ** 31 - 1), block_table.data_ptr(),
-                context_lens.data_ptr(), max_blocks, k_cache.data_ptr(), v_cache.data_ptr())
-        dims = (B, Hq, Hk, D, page, num_blocks, stream_ptr(qkv.device))
-        if fp8:
-            check(lib().rca_rope_kv_append_decode_fp8(*args, k_scale.data_ptr(), v_scale.data_ptr(), *dims),
-                  "rca_rope_kv_append_decode_fp8")
-        else:
-            check(lib().rca_rope_kv_append_decode(*args, *dims), "rca_rope_kv_append_decode")
+    if _paged_kernel_ok(qkv, k_cache, Hq, Hk, D, cs.dtype == torch.float32, cs.is_contiguous(),
+                        cs.data_ptr() % 16 == 0, B * (Hq + 2 * Hk) * (D // 16) < 2 ** 31):
+        check(lib().rca_rope_kv_append_decode(qkv.data_ptr(), qkv.stride(0), cs.data_ptr(),
+                                              min(cs.shape[0], 2 ** 31 - 1), block_table.data_ptr(),
+                                              context_lens.data_ptr(), max_blocks, k_cache.data_ptr(),
+                                              v_cache.data_ptr(), _p(k_scale), _p(v_scale), B, Hq, Hk, D, page,
+                                              num_blocks, stream_ptr(qkv.device)), "rca_rope_kv_append_decode")
         return qkv
     n = context_lens.long()
     active = (n >= 1) & (n <= max_blocks * page) & (n <= cs.shape[0])
@@ -1240,12 +1228,17 @@ def _check_paged_attention(letter, q, k_cache, v_cache, block_table, context_len
     return B
 
 
+def _paged_kernel_ok(x, k_cache, Hq, Hk, D, *more) -> bool:
+    """Whether the gfx950 paged KV kernels take this call (otherwise: the reference). ``x`` is the
+    ``q`` / ``qkv`` operand; ``more``: what an op requires beyond the shared conditions."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and paged_decode_supported(k_cache.shape[1], D, Hq, Hk)
+            and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and all(more))
+
+
 def _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D, *more) -> bool:
-    """Whether the gfx950 paged attention kernels take this call (otherwise: the reference)."""
-    num_blocks, page = k_cache.shape[0], k_cache.shape[1]
-    return (q.is_cuda and q.dtype == torch.bfloat16 and paged_decode_supported(page, D, Hq, Hk)
-            and q.stride(0) % 8 == 0 and q.data_ptr() % 16 == 0 and B <= 65535 and Hk <= 65535 and num_blocks > 0
-            and all(more))
+    """``_paged_kernel_ok`` for the attention ops: ``B`` and ``Hk`` are grid dimensions, and the
+    cache has blocks."""
+    return _paged_kernel_ok(q, k_cache, Hq, Hk, D, B <= 65535, Hk <= 65535, k_cache.shape[0] > 0, *more)
 
 
 def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens, Hq: int, Hk: int, D: int,
@@ -1285,18 +1278,10 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
         # work on this stream)
         part_o = torch.empty(B, Hq, num_splits, D, device=q.device, dtype=torch.float32)
         part_ml = torch.empty(B, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
-    if k_scale is not None:
-        check(L.rca_attn_decode_paged_fp8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                          k_scale.data_ptr(), v_scale.data_ptr(), block_table.data_ptr(),
-                                          context_lens.data_ptr(), out.data_ptr(), _p(part_o), _p(part_ml), B, Hq, Hk,
-                                          D, page, max_blocks, num_blocks, scale, num_splits, stream_ptr(q.device)),
-              "rca_attn_decode_paged_fp8")
-        del part_o, part_ml
-        return out
-    check(L.rca_attn_decode_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                  block_table.data_ptr(), context_lens.data_ptr(), out.data_ptr(), _p(part_o),
-                                  _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale, num_splits,
-                                  stream_ptr(q.device)), "rca_attn_decode_paged")
+    check(L.rca_attn_decode_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), _p(k_scale),
+                                  _p(v_scale), block_table.data_ptr(), context_lens.data_ptr(), out.data_ptr(),
+                                  _p(part_o), _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale,
+                                  num_splits, stream_ptr(q.device)), "rca_attn_decode_paged")
     del part_o, part_ml
     return out
 
@@ -1353,33 +1338,16 @@ def paged_attention_extend(q_or_qkv, k_cache, v_cache, block_table, context_lens
     if num_splits is None:
         num_splits = paged_extend_num_splits(B, Hk, max_q_len, Hq // Hk, max_blocks * page, page)
     num_splits = int(num_splits)
-    if k_scale is not None:
-        part_o = part_ml = None
-        if num_splits > 1:
-            part_o = torch.empty(T, Hq, num_splits, D, device=q.device, dtype=torch.float32)
-            part_ml = torch.empty(T, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
-        check(lib().rca_attn_extend_paged_fp8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                              k_scale.data_ptr(), v_scale.data_ptr(), block_table.data_ptr(),
-                                              context_lens.data_ptr(), cu_q_lens.data_ptr(), out.data_ptr(),
-                                              _p(part_o), _p(part_ml), B, T, max_q_len, Hq, Hk, D, page, max_blocks,
-                                              num_blocks, scale, num_splits, stream_ptr(q.device)),
-              "rca_attn_extend_paged_fp8")
-        del part_o, part_ml
-        return out
-    if num_splits == 1:
-        check(lib().rca_attn_extend_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                          block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
-                                          out.data_ptr(), B, max_q_len, Hq, Hk, D, page, max_blocks, num_blocks,
-                                          scale, stream_ptr(q.device)), "rca_attn_extend_paged")
-        return out
-    # transient, stream-ordered workspaces, as in paged_attention_decode
-    part_o = torch.empty(T, Hq, num_splits, D, device=q.device, dtype=torch.float32)
-    part_ml = torch.empty(T, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
-    check(lib().rca_attn_extend_paged_split(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                            block_table.data_ptr(), context_lens.data_ptr(), cu_q_lens.data_ptr(),
-                                            out.data_ptr(), part_o.data_ptr(), part_ml.data_ptr(), B, T, max_q_len, Hq,
-                                            Hk, D, page, max_blocks, num_blocks, scale, num_splits,
-                                            stream_ptr(q.device)), "rca_attn_extend_paged_split")
+    part_o = part_ml = None
+    if num_splits > 1:
+        # transient, stream-ordered workspaces, as in paged_attention_decode
+        part_o = torch.empty(T, Hq, num_splits, D, device=q.device, dtype=torch.float32)
+        part_ml = torch.empty(T, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
+    check(lib().rca_attn_extend_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), _p(k_scale),
+                                      _p(v_scale), block_table.data_ptr(), context_lens.data_ptr(),
+                                      cu_q_lens.data_ptr(), out.data_ptr(), _p(part_o), _p(part_ml), B, T, max_q_len,
+                                      Hq, Hk, D, page, max_blocks, num_blocks, scale, num_splits,
+                                      stream_ptr(q.device)), "rca_attn_extend_paged")
     del part_o, part_ml
     return out
 

@@ -18,6 +18,8 @@ c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
 c_ll = ctypes.c_longlong
 c_float = ctypes.c_float
+_KV = [c_void_p, c_void_p, c_void_p, c_void_p]  # k_cache, v_cache, k_scale, v_scale of the paged KV ops (csrc/paged_kv.h)
+_TAIL = [c_int, c_int, c_int, c_float, c_int, c_void_p]  # page_size, max_blocks, num_blocks, scale, num_splits, stream
 
 _SIGS = {
     "rca_rmsnorm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
@@ -78,18 +80,19 @@ _SIGS = {
                               c_void_p]),
     "rca_image_normalize": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                      c_void_p]),
-    "rca_kv_cache_append": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_ll,
-                                    c_void_p]),
-    "rca_attn_decode_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 7 + [c_int] * 7 + [c_float, c_int, c_void_p]),
+    "rca_kv_cache_append": (c_int, [c_void_p, c_ll, c_void_p, *_KV,  # qkv, row_stride, slot_mapping
+        c_ll, c_int, c_int, c_int, c_ll, c_void_p]),  # T, Hq, Hk, D, num_slots, stream
+    "rca_rope_kv_append_decode": (c_int, [c_void_p, c_ll, c_void_p, c_int,  # qkv, row_stride, cs, max_pos
+        c_void_p, c_void_p, c_int, *_KV,  # block_table, context_lens, max_blocks
+        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),  # B, Hq, Hk, D, page_size, num_blocks, stream
+    "rca_attn_decode_paged": (c_int, [c_void_p, c_ll, *_KV,  # q, q_stride
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,  # block_table, context_lens, out, part_o, part_ml
+        c_int, c_int, c_int, c_int, *_TAIL]),  # B, Hq, Hk, D
+    "rca_attn_extend_paged": (c_int, [c_void_p, c_ll, *_KV,  # q, q_stride
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,  # block_table, context_lens, cu_q_lens, out, part_o, part_ml
+        c_int, c_ll, c_int, c_int, c_int, c_int, *_TAIL]),  # B, T, max_q_len, Hq, Hk, D
     "rca_attn_decode_num_splits": (c_int, [c_int] * 4),
-    "rca_kv_cache_append_fp8": (c_int, [c_void_p, c_ll] + [c_void_p] * 5 + [c_ll, c_int, c_int, c_int, c_ll, c_void_p]),
-    "rca_attn_decode_paged_fp8": (c_int, [c_void_p, c_ll] + [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "rca_attn_decode_fp8_set_step": (c_int, [c_int]),
-    "rca_attn_extend_paged_fp8": (c_int, [c_void_p, c_ll] + [c_void_p] * 10 + [c_int, c_ll] + [c_int] * 7
-                                  + [c_float, c_int, c_void_p]),
-    "rca_attn_extend_paged": (c_int, [c_void_p, c_ll] + [c_void_p] * 6 + [c_int] * 8 + [c_float, c_void_p]),
-    "rca_attn_extend_paged_split": (c_int, [c_void_p, c_ll] + [c_void_p] * 8 + [c_int, c_ll] + [c_int] * 7
-                                    + [c_float, c_int, c_void_p]),
     "rca_attn_extend_num_splits": (c_int, [c_int] * 6),
     "rca_sample_logits": (c_int, [c_void_p, c_ll, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rca_penalize_logits": (c_int, [c_void_p, c_ll, c_int] + [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p]),
@@ -100,10 +103,6 @@ _SIGS = {
     "rca_lora_splits": (c_int, [c_int, c_int]),
     "rca_lora_add": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_int, c_void_p, c_ll] + [c_int] * 5
                      + [c_void_p]),
-    "rca_rope_kv_append_decode": (c_int, [c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-                                  + [c_int] * 6 + [c_void_p]),
-    "rca_rope_kv_append_decode_fp8": (c_int, [c_void_p, c_ll, c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4
-                                      + [c_int] * 6 + [c_void_p]),
 }
 
 

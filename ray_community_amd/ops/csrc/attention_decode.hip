@@ -16,8 +16,12 @@
 // Masking is by loop bounds and by not loading: a token at position >= context_lens[b] is never
 // read (its lanes get zero K/V and a -inf score), and block_table[b, j] is read only for
 // j < ceil(context_lens[b] / page_size), so NaN/Inf garbage in dead slots cannot reach the output.
+//
+// The entry points at the end, rca_kv_cache_append and rca_attn_decode_paged, serve both cache
+// kinds: the e4m3 kernels and their launchers are in attention_decode_fp8.hip (paged_kv.h).
 #include "attention_combine.h"
 #include "attention_common.h"
+#include "paged_kv.h"
 
 namespace {
 
@@ -245,33 +249,6 @@ __global__ __launch_bounds__(256) void kv_cache_append_kernel(const bf16_t* __re
   *reinterpret_cast<u32x4*>(dst) = x;
 }
 
-template <int D, int G>
-int launch_decode(const bf16_t* q, long q_stride, const bf16_t* kc, const bf16_t* vc, const int* bt, const int* cl,
-                  int max_blocks, int num_blocks, int page_size, int B, int Hk, float scale_log2, int num_splits,
-                  bf16_t* out, float* part_o, float* part_ml, hipStream_t stream) {
-  hipLaunchKernelGGL((attn_decode_paged_kernel<D, G>), dim3(num_splits, Hk, B), dim3(256), 0, stream, q, q_stride, kc,
-                     vc, bt, cl, max_blocks, num_blocks, page_size, Hk, scale_log2, num_splits, out, part_o, part_ml);
-  return (int)hipGetLastError();
-}
-
-template <int D>
-int launch_decode_g(int G, const bf16_t* q, long q_stride, const bf16_t* kc, const bf16_t* vc, const int* bt,
-                    const int* cl, int max_blocks, int num_blocks, int page_size, int B, int Hk, float scale_log2,
-                    int num_splits, bf16_t* out, float* part_o, float* part_ml, hipStream_t stream) {
-#define RCA_DEC(GG)                                                                                                \
-  case GG:                                                                                                         \
-    return launch_decode<D, GG>(q, q_stride, kc, vc, bt, cl, max_blocks, num_blocks, page_size, B, Hk, scale_log2, \
-                                num_splits, out, part_o, part_ml, stream)
-  switch (G) {
-    RCA_DEC(1);
-    RCA_DEC(2);
-    RCA_DEC(4);
-    RCA_DEC(8);
-  }
-#undef RCA_DEC
-  return -1;
-}
-
 }  // namespace
 
 // Default split count of the paged decode. Heuristic:
@@ -293,50 +270,67 @@ RCA_API int rca_attn_decode_num_splits(int B, int Hk, int max_context, int page_
   return (int)n;
 }
 
-// qkv: [T, >= (Hq+2Hk)*D] bf16 with row stride `row_stride` elements (K heads at column Hq*D, V heads
-// after them); slot_mapping: int32 [T], -1 = skip; caches: bf16 [num_blocks, page_size, Hk, D].
-RCA_API int rca_kv_cache_append(const void* qkv, long long row_stride, const int* slot_mapping, void* k_cache,
-                                void* v_cache, long long T, int Hq, int Hk, int D, long long num_slots,
-                                hipStream_t stream) {
-  if (T == 0) return 0;
-  if (T < 0 || Hq <= 0 || Hk <= 0 || D <= 0 || (D & 7) || (row_stride & 7) || num_slots < 0) return -1;
-  if (row_stride < (long long)(Hq + 2 * Hk) * D) return -1;
-  if (((uintptr_t)qkv | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) return -3;
-  const int kv_chunks = Hk * D / 8;
-  const long long n = T * 2 * kv_chunks;
-  const long long blocks = (n + 255) / 256;
-  if (blocks >= (1LL << 31)) return -2;
-  hipLaunchKernelGGL(kv_cache_append_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const bf16_t*)qkv,
-                     (long)row_stride, slot_mapping, (bf16_t*)k_cache, (bf16_t*)v_cache, (long)T, kv_chunks, Hq * D,
-                     (long)num_slots);
+int launch_kv_append_bf16(const void* qkv, long long row_stride, const int* slot_mapping, void* k_cache, void* v_cache,
+                          void*, void*, long long T, int Hq, int Hk, int D, long long num_slots, unsigned blocks,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(kv_cache_append_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)qkv, (long)row_stride,
+                     slot_mapping, (bf16_t*)k_cache, (bf16_t*)v_cache, (long)T, Hk * D / 8, Hq * D, (long)num_slots);
   return (int)hipGetLastError();
 }
 
-// q: logical [B, Hq, D] bf16 at q + b*q_stride + h*D (q_stride in elements: Hq*D for a contiguous q,
-// (Hq+2Hk)*D to read it in place from the fused qkv row). out: bf16 [B, Hq*D]. num_splits > 1 needs
-// part_o (fp32 [B, Hq, num_splits, D]) and part_ml (fp32 [B, Hq, num_splits, 2] = (m, l)).
-RCA_API int rca_attn_decode_paged(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
-                                  const int* block_table, const int* context_lens, void* out, void* part_o,
-                                  void* part_ml, int B, int Hq, int Hk, int D, int page_size, int max_blocks,
-                                  int num_blocks, float scale, int num_splits, hipStream_t stream) {
-  if (B == 0) return 0;
-  if (B < 0 || Hq <= 0 || Hk <= 0 || Hq % Hk || (D != 64 && D != 128)) return -1;
-  if (page_size <= 0 || (page_size & 15) || max_blocks <= 0 || num_blocks <= 0 || num_splits < 1) return -1;
-  if (q_stride < (long long)Hq * D || (q_stride & 7)) return -1;
-  if (B > 65535 || Hk > 65535) return -2;
-  if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) return -3;
-  if (num_splits > 1 && (!part_o || !part_ml || (((uintptr_t)part_o | (uintptr_t)part_ml) & 15))) return -3;
-  const float scale_log2 = scale * 1.44269504088896340736f;
-  int rc;
-  if (D == 128)
-    rc = launch_decode_g<128>(Hq / Hk, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache,
-                              (const bf16_t*)v_cache, block_table, context_lens, max_blocks, num_blocks, page_size, B,
-                              Hk, scale_log2, num_splits, (bf16_t*)out, (float*)part_o, (float*)part_ml, stream);
-  else
-    rc = launch_decode_g<64>(Hq / Hk, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache,
-                             block_table, context_lens, max_blocks, num_blocks, page_size, B, Hk, scale_log2,
-                             num_splits, (bf16_t*)out, (float*)part_o, (float*)part_ml, stream);
+int launch_attn_decode_bf16(const void* q, long long q_stride, const void* k_cache, const void* v_cache, const void*,
+                            const void*, const int* block_table, const int* context_lens, void* out, void* part_o,
+                            void* part_ml, int B, int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
+                            float scale, int num_splits, hipStream_t stream) {
+  const int rc = paged_kv::dispatch_dg(D, Hq / Hk, [&](auto d, auto g) {
+    hipLaunchKernelGGL((attn_decode_paged_kernel<d.value, g.value>), dim3(num_splits, Hk, B), dim3(256), 0, stream,
+                       (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_table,
+                       context_lens, max_blocks, num_blocks, page_size, Hk, scale * paged_kv::kLog2e, num_splits,
+                       (bf16_t*)out, (float*)part_o, (float*)part_ml);
+    return (int)hipGetLastError();
+  });
   if (rc != 0 || num_splits == 1) return rc;
   return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)B * Hq, num_splits, D,
                               stream);
+}
+
+// qkv: [T, >= (Hq+2Hk)*D] bf16 with row stride `row_stride` elements (a multiple of 8; K heads at
+// column Hq*D, V heads after them), 16-B aligned; slot_mapping: int32 [T], -1 = skip; caches and
+// scales: either kind (paged_kv.h), num_slots = num_blocks * page_size. D is any multiple of 8; the
+// e4m3 cache needs D / 8 to be a power of two <= 64 (the lanes that reduce a head row's amax).
+RCA_API int rca_kv_cache_append(const void* qkv, long long row_stride, const int* slot_mapping, void* k_cache,
+                                void* v_cache, void* k_scale, void* v_scale, long long T, int Hq, int Hk, int D,
+                                long long num_slots, hipStream_t stream) {
+  if (T == 0 || num_slots == 0) return 0;  // no token, or no slot a token could go to (a cache of no blocks)
+  if (T < 0 || !paged_kv::heads_ok(Hq, Hk) || D <= 0 || (D & 7) || num_slots < 0) return -1;
+  if (!paged_kv::rows_ok(row_stride, (long long)(Hq + 2 * Hk) * D)) return -1;
+  const int lpt = D / 8;
+  if ((k_scale || v_scale) && ((lpt & (lpt - 1)) || lpt > 64)) return -1;
+  const long long blocks = (T * 2 * Hk * lpt + 255) / 256;
+  if (blocks >= (1LL << 31)) return -2;
+  if (!paged_kv::all_set(qkv, slot_mapping) || !paged_kv::aligned(16, qkv)) return -3;
+  if (!paged_kv::caches_ok(k_cache, v_cache, k_scale, v_scale)) return -3;
+  return (k_scale ? launch_kv_append_fp8 : launch_kv_append_bf16)(qkv, row_stride, slot_mapping, k_cache, v_cache,
+                                                                  k_scale, v_scale, T, Hq, Hk, D, num_slots,
+                                                                  (unsigned)blocks, stream);
+}
+
+// q: logical [B, Hq, D] bf16 at q + b*q_stride + h*D (q_stride in elements: Hq*D for a contiguous q,
+// (Hq+2Hk)*D to read it in place from the fused qkv row). block_table: int32 [B, max_blocks];
+// context_lens: int32 [B]; caches and scales: either kind (paged_kv.h). out: bf16 [B, Hq*D].
+// num_splits > 1 needs part_o (fp32 [B, Hq, num_splits, D]) and part_ml (fp32 [B, Hq, num_splits, 2]
+// = (m, l)). D is 64 or 128, Hq / Hk one of 1, 2, 4, 8, page_size a multiple of 16.
+RCA_API int rca_attn_decode_paged(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
+                                  const void* k_scale, const void* v_scale, const int* block_table,
+                                  const int* context_lens, void* out, void* part_o, void* part_ml, int B, int Hq,
+                                  int Hk, int D, int page_size, int max_blocks, int num_blocks, float scale,
+                                  int num_splits, hipStream_t stream) {
+  if (B == 0) return 0;
+  if (!paged_kv::attn_shape_ok(B, Hq, Hk, D, q_stride, page_size, max_blocks, num_blocks, num_splits)) return -1;
+  if (!paged_kv::grid_ok(B, Hk)) return -2;
+  if (!paged_kv::caches_ok(k_cache, v_cache, k_scale, v_scale)) return -3;
+  if (!paged_kv::attn_ptrs_ok(q, out, block_table, context_lens, part_o, part_ml, num_splits)) return -3;
+  return (k_scale ? launch_attn_decode_fp8 : launch_attn_decode_bf16)(
+      q, q_stride, k_cache, v_cache, k_scale, v_scale, block_table, context_lens, out, part_o, part_ml, B, Hq, Hk, D,
+      page_size, max_blocks, num_blocks, scale, num_splits, stream);
 }

@@ -1,5 +1,7 @@
 // FP8 paged KV cache for gfx950: the quantising cache append and the single-token (decode)
-// attention over it. The bf16 counterparts are in attention_decode.hip.
+// attention over it. The bf16 counterparts are in attention_decode.hip, and so are the entry points
+// of both kinds, rca_kv_cache_append and rca_attn_decode_paged, which reach the launchers at the end
+// of this file when they are given scales (paged_kv.h).
 //
 // Cache layout per layer: k_cache, v_cache = OCP e4m3 bytes [num_blocks, page_size, Hk, D] with the
 // slot arithmetic of the bf16 cache (slot = block * page_size + offset), plus k_scale, v_scale =
@@ -33,6 +35,7 @@
 // (blk * page_size + off + t) * Hk + hk under the same bounds.
 #include "attention_decode_merge.h"
 #include "kv_fp8.h"
+#include "paged_kv.h"
 
 namespace {
 
@@ -237,28 +240,6 @@ __global__ __launch_bounds__(256) void kv_cache_append_fp8_kernel(const bf16_t* 
 
 int g_dec_fp8_groups = 2;  // 16-token groups per wave step: rca_attn_decode_fp8_set_step
 
-template <int D, int G, int NG>
-int launch_decode_fp8(const bf16_t* q, long q_stride, const fp8_t* kc, const fp8_t* vc, const float* ksc,
-                      const float* vsc, const int* bt, const int* cl, int max_blocks, int num_blocks, int page_size,
-                      int B, int Hk, float scale_log2, int num_splits, bf16_t* out, float* part_o, float* part_ml,
-                      hipStream_t stream) {
-  hipLaunchKernelGGL((attn_decode_paged_fp8_kernel<D, G, NG>), dim3(num_splits, Hk, B), dim3(256), 0, stream, q,
-                     q_stride, kc, vc, ksc, vsc, bt, cl, max_blocks, num_blocks, page_size, Hk, scale_log2, num_splits,
-                     out, part_o, part_ml);
-  return (int)hipGetLastError();
-}
-
-template <int D, int NG, typename... A>
-int launch_decode_fp8_g(int G, A... a) {
-  switch (G) {
-    case 1: return launch_decode_fp8<D, 1, NG>(a...);
-    case 2: return launch_decode_fp8<D, 2, NG>(a...);
-    case 4: return launch_decode_fp8<D, 4, NG>(a...);
-    case 8: return launch_decode_fp8<D, 8, 1>(a...);  // 32 tokens of s and p for 8 rows do not fit the VGPRs
-  }
-  return -1;
-}
-
 }  // namespace
 
 // Tokens per wave step of the fp8 decode kernel: 32 (default) or 16. A measurement knob
@@ -269,70 +250,47 @@ RCA_API int rca_attn_decode_fp8_set_step(int tokens) {
   return 0;
 }
 
-// rca_kv_cache_append over the fp8 cache: qkv as there (bf16, any row stride that is a multiple of
-// 8); caches: e4m3 bytes [num_blocks, page_size, Hk, D]; scales: fp32 [num_blocks, page_size, Hk].
-// D / 8 must be a power of two <= 64.
-RCA_API int rca_kv_cache_append_fp8(const void* qkv, long long row_stride, const int* slot_mapping, void* k_cache,
-                                    void* v_cache, void* k_scale, void* v_scale, long long T, int Hq, int Hk, int D,
-                                    long long num_slots, hipStream_t stream) {
-  if (T == 0) return 0;
-  if (T < 0 || Hq <= 0 || Hk <= 0 || D <= 0 || (D & 7) || (row_stride & 7) || num_slots < 0) return -1;
-  const int lpt = D / 8;
-  if ((lpt & (lpt - 1)) || lpt > 64) return -1;
-  if (row_stride < (long long)(Hq + 2 * Hk) * D) return -1;
-  if ((uintptr_t)qkv & 15) return -3;
-  if (((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) return -3;
-  if (!k_scale || !v_scale || (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)) return -3;
-  const long long n = T * 2 * Hk * lpt;
-  const long long blocks = (n + 255) / 256;
-  if (blocks >= (1LL << 31)) return -2;
-#define RCA_APP(L)                                                                                                 \
-  case L:                                                                                                          \
-    hipLaunchKernelGGL(kv_cache_append_fp8_kernel<L>, dim3((unsigned)blocks), dim3(256), 0, stream,                \
-                       (const bf16_t*)qkv, (long)row_stride, slot_mapping, (fp8_t*)k_cache, (fp8_t*)v_cache,       \
-                       (float*)k_scale, (float*)v_scale, (long)T, Hk, Hq * D, (long)num_slots);                    \
-    break
-  switch (lpt) {
-    RCA_APP(1);
-    RCA_APP(2);
-    RCA_APP(4);
-    RCA_APP(8);
-    RCA_APP(16);
-    RCA_APP(32);
-    RCA_APP(64);
+// rca_kv_cache_append (attention_decode.hip) over the e4m3 cache. D / 8 is a power of two <= 64.
+int launch_kv_append_fp8(const void* qkv, long long row_stride, const int* slot_mapping, void* k_cache, void* v_cache,
+                         void* k_scale, void* v_scale, long long T, int Hq, int Hk, int D, long long num_slots,
+                         unsigned blocks, hipStream_t stream) {
+  auto launch = [&](auto lpt) {
+    hipLaunchKernelGGL(kv_cache_append_fp8_kernel<lpt.value>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)qkv,
+                       (long)row_stride, slot_mapping, (fp8_t*)k_cache, (fp8_t*)v_cache, (float*)k_scale,
+                       (float*)v_scale, (long)T, Hk, Hq * D, (long)num_slots);
+    return (int)hipGetLastError();
+  };
+  using namespace paged_kv;
+  switch (D / 8) {
+    case 1: return launch(int_c<1>{});
+    case 2: return launch(int_c<2>{});
+    case 4: return launch(int_c<4>{});
+    case 8: return launch(int_c<8>{});
+    case 16: return launch(int_c<16>{});
+    case 32: return launch(int_c<32>{});
+    case 64: return launch(int_c<64>{});
   }
-#undef RCA_APP
-  return (int)hipGetLastError();
+  return -1;
 }
 
-// rca_attn_decode_paged over the fp8 cache (k_scale, v_scale: fp32 [num_blocks, page_size, Hk]);
-// q, out, the workspaces and every other argument as there.
-RCA_API int rca_attn_decode_paged_fp8(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
-                                      const void* k_scale, const void* v_scale, const int* block_table,
-                                      const int* context_lens, void* out, void* part_o, void* part_ml, int B, int Hq,
-                                      int Hk, int D, int page_size, int max_blocks, int num_blocks, float scale,
-                                      int num_splits, hipStream_t stream) {
-  if (B == 0) return 0;
-  if (B < 0 || Hq <= 0 || Hk <= 0 || Hq % Hk || (D != 64 && D != 128)) return -1;
-  if (page_size <= 0 || (page_size & 15) || max_blocks <= 0 || num_blocks <= 0 || num_splits < 1) return -1;
-  if (q_stride < (long long)Hq * D || (q_stride & 7)) return -1;
-  if (B > 65535 || Hk > 65535) return -2;
-  if (((uintptr_t)q | (uintptr_t)out) & 15) return -3;
-  if (((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) return -3;
-  if (!k_scale || !v_scale || (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)) return -3;
-  if (num_splits > 1 && (!part_o || !part_ml || (((uintptr_t)part_o | (uintptr_t)part_ml) & 15))) return -3;
-  const float scale_log2 = scale * 1.44269504088896340736f;
-  const int G = Hq / Hk;
-#define RCA_DEC8_ARGS                                                                                              \
-  G, (const bf16_t*)q, (long)q_stride, (const fp8_t*)k_cache, (const fp8_t*)v_cache, (const float*)k_scale,        \
-      (const float*)v_scale, block_table, context_lens, max_blocks, num_blocks, page_size, B, Hk, scale_log2,      \
-      num_splits, (bf16_t*)out, (float*)part_o, (float*)part_ml, stream
-  int rc;
-  if (g_dec_fp8_groups == 2)
-    rc = D == 128 ? launch_decode_fp8_g<128, 2>(RCA_DEC8_ARGS) : launch_decode_fp8_g<64, 2>(RCA_DEC8_ARGS);
-  else
-    rc = D == 128 ? launch_decode_fp8_g<128, 1>(RCA_DEC8_ARGS) : launch_decode_fp8_g<64, 1>(RCA_DEC8_ARGS);
-#undef RCA_DEC8_ARGS
+// rca_attn_decode_paged (attention_decode.hip) over the e4m3 cache.
+int launch_attn_decode_fp8(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
+                           const void* k_scale, const void* v_scale, const int* block_table, const int* context_lens,
+                           void* out, void* part_o, void* part_ml, int B, int Hq, int Hk, int D, int page_size,
+                           int max_blocks, int num_blocks, float scale, int num_splits, hipStream_t stream) {
+  auto launch = [&](auto ng) {
+    return paged_kv::dispatch_dg(D, Hq / Hk, [&](auto d, auto g) {
+      // G = 8: 32 tokens of s and p for 8 rows do not fit the VGPRs
+      constexpr int NG = g.value == 8 ? 1 : ng.value;
+      hipLaunchKernelGGL((attn_decode_paged_fp8_kernel<d.value, g.value, NG>), dim3(num_splits, Hk, B), dim3(256), 0,
+                         stream, (const bf16_t*)q, (long)q_stride, (const fp8_t*)k_cache, (const fp8_t*)v_cache,
+                         (const float*)k_scale, (const float*)v_scale, block_table, context_lens, max_blocks,
+                         num_blocks, page_size, Hk, scale * paged_kv::kLog2e, num_splits, (bf16_t*)out,
+                         (float*)part_o, (float*)part_ml);
+      return (int)hipGetLastError();
+    });
+  };
+  const int rc = g_dec_fp8_groups == 2 ? launch(paged_kv::int_c<2>{}) : launch(paged_kv::int_c<1>{});
   if (rc != 0 || num_splits == 1) return rc;
   return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)B * Hq, num_splits, D,
                               stream);

@@ -59,8 +59,12 @@
 // O row. Rows past n_b*G are not stored at all, as in the unsplit kernel. The workspace addresses
 // are the out address's (q0 + tok, hq) with the split index inside, so they stay inside
 // [T, Hq, num_splits, *] under the same cu_q_lens contract.
+//
+// The entry point at the end, rca_attn_extend_paged, serves both cache kinds: the e4m3 kernel and
+// its launcher are in attention_extend_fp8.hip (paged_kv.h).
 #include "attention_combine.h"
 #include "attention_common.h"
+#include "paged_kv.h"
 
 namespace {
 
@@ -325,56 +329,6 @@ RCA_EXT_INST(128, 8)
 #undef RCA_EXT_INST
 #undef RCA_EXT_INST1
 
-template <int D, bool SPLIT>
-int launch_extend_g(int G, dim3 grid, hipStream_t stream, const bf16_t* q, long q_stride, const bf16_t* kc,
-                    const bf16_t* vc, const int* bt, const int* cl, const int* cu, bf16_t* out, int max_q_len, int Hk,
-                    int page, int max_blocks, int num_blocks, float scale2, float* part_o, float* part_ml,
-                    int num_splits) {
-#define RCA_EXT(GG)                                                                                              \
-  case GG:                                                                                                       \
-    hipLaunchKernelGGL((attn_extend_paged_kernel<D, GG, SPLIT>), grid, dim3(kThreads), 0, stream, q, q_stride, kc, \
-                       vc, bt, cl, cu, out, max_q_len, Hk, page, max_blocks, num_blocks, scale2, part_o, part_ml,  \
-                       num_splits);                                                                              \
-    return (int)hipGetLastError()
-  switch (G) {
-    RCA_EXT(1);
-    RCA_EXT(2);
-    RCA_EXT(4);
-    RCA_EXT(8);
-  }
-#undef RCA_EXT
-  return -1;
-}
-
-// The checks and the launch both entry points share. T (rows of q, out and the workspaces) is only
-// read when num_splits > 1.
-int extend_launch(const void* q, long long q_stride, const void* k_cache, const void* v_cache, const int* block_table,
-                  const int* context_lens, const int* cu_q_lens, void* out, void* part_o, void* part_ml, int B,
-                  long long T, int max_q_len, int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
-                  float scale, int num_splits, hipStream_t stream) {
-  if (B == 0 || max_q_len == 0) return 0;
-  if (B < 0 || max_q_len < 0 || Hq <= 0 || Hk <= 0 || Hq % Hk || (D != 64 && D != 128)) return -1;
-  if (page_size <= 0 || (page_size & 15) || max_blocks <= 0 || num_blocks <= 0 || !(scale > 0.f)) return -1;
-  if (q_stride < (long long)Hq * D || (q_stride & 7) || num_splits < 1 || (num_splits > 1 && T < 0)) return -1;
-  const int G = Hq / Hk;
-  const long long tiles = ((long long)max_q_len * G + 127) / 128 * num_splits;
-  if (B > 65535 || Hk > 65535 || tiles >= (1LL << 31) || (long long)num_blocks * page_size >= (1LL << 31)) return -2;
-  if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) return -3;
-  if (num_splits > 1 && (!part_o || !part_ml || (((uintptr_t)part_o | (uintptr_t)part_ml) & 15))) return -3;
-  const float scale2 = scale * 1.44269504088896340736f;
-  const dim3 grid((unsigned)tiles, Hk, B);
-#define RCA_EXT_ARGS                                                                                              \
-  G, grid, stream, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache, (const bf16_t*)v_cache, block_table, \
-      context_lens, cu_q_lens, (bf16_t*)out, max_q_len, Hk, page_size, max_blocks, num_blocks, scale2,            \
-      (float*)part_o, (float*)part_ml, num_splits
-  if (num_splits == 1) return D == 128 ? launch_extend_g<128, false>(RCA_EXT_ARGS) : launch_extend_g<64, false>(RCA_EXT_ARGS);
-  const int rc = D == 128 ? launch_extend_g<128, true>(RCA_EXT_ARGS) : launch_extend_g<64, true>(RCA_EXT_ARGS);
-#undef RCA_EXT_ARGS
-  if (rc != 0 || T == 0) return rc;
-  return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)T * Hq, num_splits, D,
-                              stream);
-}
-
 }  // namespace
 
 // Default split count of the paged extend. The unsplit grid is row_tiles * Hk * B workgroups
@@ -400,28 +354,52 @@ RCA_API int rca_attn_extend_num_splits(int B, int Hk, int max_q_len, int G, int 
   return (int)n;
 }
 
-// q: packed query rows, row t at q + t*q_stride (+ h*D per head; q_stride in elements: Hq*D for a
-// contiguous q, (Hq+2Hk)*D to read it in place from the fused qkv row). cu_q_lens: int32 [B+1],
-// non-decreasing, cu_q_lens[B] <= rows of q and out; max_q_len >= every chunk length (host side:
-// it sizes the grid). context_lens counts each sequence's cached tokens including its chunk.
-// out: bf16 [T, Hq*D]; rows no sequence owns are not written. scale must be > 0.
-RCA_API int rca_attn_extend_paged(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
-                                  const int* block_table, const int* context_lens, const int* cu_q_lens, void* out,
-                                  int B, int max_q_len, int Hq, int Hk, int D, int page_size, int max_blocks,
-                                  int num_blocks, float scale, hipStream_t stream) {
-  return extend_launch(q, q_stride, k_cache, v_cache, block_table, context_lens, cu_q_lens, out, nullptr, nullptr, B,
-                       0, max_q_len, Hq, Hk, D, page_size, max_blocks, num_blocks, scale, 1, stream);
+int launch_attn_extend_bf16(const void* q, long long q_stride, const void* k_cache, const void* v_cache, const void*,
+                            const void*, const int* block_table, const int* context_lens, const int* cu_q_lens,
+                            void* out, void* part_o, void* part_ml, int B, long long T, int max_q_len, int Hq, int Hk,
+                            int D, int page_size, int max_blocks, int num_blocks, float scale, int num_splits,
+                            unsigned tiles, hipStream_t stream) {
+  const int rc = with_bool(num_splits > 1, [&](auto split) {
+    return paged_kv::dispatch_dg(D, Hq / Hk, [&](auto d, auto g) {
+      hipLaunchKernelGGL((attn_extend_paged_kernel<d.value, g.value, split.value>), dim3(tiles, Hk, B),
+                         dim3(kThreads), 0, stream, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache,
+                         (const bf16_t*)v_cache, block_table, context_lens, cu_q_lens, (bf16_t*)out, max_q_len, Hk,
+                         page_size, max_blocks, num_blocks, scale * paged_kv::kLog2e, (float*)part_o, (float*)part_ml,
+                         num_splits);
+      return (int)hipGetLastError();
+    });
+  });
+  if (rc != 0 || num_splits == 1 || T == 0) return rc;
+  return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)T * Hq, num_splits, D,
+                              stream);
 }
 
-// The same over num_splits splits of every row tile's keys, merged in split order (deterministic,
-// no atomics). T = rows of q and out; num_splits > 1 needs part_o (fp32 [T, Hq, num_splits, D]) and
-// part_ml (fp32 [T, Hq, num_splits, 2] = (m, l)), and then rows of out that no sequence owns are
-// written with whatever the workspace held. num_splits == 1 is rca_attn_extend_paged.
-RCA_API int rca_attn_extend_paged_split(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
-                                        const int* block_table, const int* context_lens, const int* cu_q_lens,
-                                        void* out, void* part_o, void* part_ml, int B, long long T, int max_q_len,
-                                        int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
-                                        float scale, int num_splits, hipStream_t stream) {
-  return extend_launch(q, q_stride, k_cache, v_cache, block_table, context_lens, cu_q_lens, out, part_o, part_ml, B, T,
-                       max_q_len, Hq, Hk, D, page_size, max_blocks, num_blocks, scale, num_splits, stream);
+// q: packed query rows, row t at q + t*q_stride (+ h*D per head; q_stride in elements: Hq*D for a
+// contiguous q, (Hq+2Hk)*D to read it in place from the fused qkv row). cu_q_lens: int32 [B+1],
+// non-decreasing, cu_q_lens[B] <= T = rows of q and out; max_q_len >= every chunk length (host side:
+// it sizes the grid). context_lens counts each sequence's cached tokens including its chunk. Caches
+// and scales: either kind (paged_kv.h). out: bf16 [T, Hq*D]. scale must be > 0.
+//
+// num_splits == 1 is the unsplit launch: no workspace, T unread, rows of out that no sequence owns
+// not written. num_splits > 1 runs that many splits of every row tile's keys, merged in split order
+// (deterministic, no atomics); it needs part_o (fp32 [T, Hq, num_splits, D]) and part_ml (fp32
+// [T, Hq, num_splits, 2] = (m, l)), and then rows of out that no sequence owns are written with
+// whatever the workspace held.
+RCA_API int rca_attn_extend_paged(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
+                                  const void* k_scale, const void* v_scale, const int* block_table,
+                                  const int* context_lens, const int* cu_q_lens, void* out, void* part_o,
+                                  void* part_ml, int B, long long T, int max_q_len, int Hq, int Hk, int D,
+                                  int page_size, int max_blocks, int num_blocks, float scale, int num_splits,
+                                  hipStream_t stream) {
+  if (B == 0 || max_q_len == 0) return 0;
+  if (!paged_kv::attn_shape_ok(B, Hq, Hk, D, q_stride, page_size, max_blocks, num_blocks, num_splits)) return -1;
+  if (max_q_len < 0 || !(scale > 0.f) || (num_splits > 1 && T < 0)) return -1;
+  const long long tiles = ((long long)max_q_len * (Hq / Hk) + 127) / 128 * num_splits;
+  if (!paged_kv::grid_ok(B, Hk) || tiles >= (1LL << 31)) return -2;
+  if ((long long)num_blocks * page_size >= (1LL << 31)) return -2;  // the kernels' slot index is an int
+  if (!paged_kv::caches_ok(k_cache, v_cache, k_scale, v_scale) || !cu_q_lens) return -3;
+  if (!paged_kv::attn_ptrs_ok(q, out, block_table, context_lens, part_o, part_ml, num_splits)) return -3;
+  return (k_scale ? launch_attn_extend_fp8 : launch_attn_extend_bf16)(
+      q, q_stride, k_cache, v_cache, k_scale, v_scale, block_table, context_lens, cu_q_lens, out, part_o, part_ml, B, T,
+      max_q_len, Hq, Hk, D, page_size, max_blocks, num_blocks, scale, num_splits, (unsigned)tiles, stream);
 }

@@ -72,10 +72,12 @@
 //
 // This file is attention_extend.hip with that stage: templating the bf16 kernel on the cache
 // element changed the scalar code of its bf16 instantiations, which are to stay as measured, so
-// the fp8 kernel is a kernel of its own.
+// the fp8 kernel is a kernel of its own. The entry point of both kinds, rca_attn_extend_paged, is
+// there too and reaches the launcher at the end of this file when it is given scales (paged_kv.h).
 #include "attention_combine.h"
 #include "attention_common.h"
 #include "kv_fp8.h"
+#include "paged_kv.h"
 
 namespace {
 
@@ -359,60 +361,25 @@ RCA_EXT_INST(128, 8)
 #undef RCA_EXT_INST
 #undef RCA_EXT_INST1
 
-template <int D, bool SPLIT>
-int launch_extend_fp8_g(int G, dim3 grid, hipStream_t stream, const bf16_t* q, long q_stride, const fp8_t* kc,
-                        const fp8_t* vc, const float* ksc, const float* vsc, const int* bt, const int* cl,
-                        const int* cu, bf16_t* out, int max_q_len, int Hk, int page, int max_blocks, int num_blocks,
-                        float scale2, float* part_o, float* part_ml, int num_splits) {
-#define RCA_EXT(GG)                                                                                                \
-  case GG:                                                                                                         \
-    hipLaunchKernelGGL((attn_extend_paged_fp8_kernel<D, GG, SPLIT>), grid, dim3(kThreads), 0, stream, q, q_stride, \
-                       kc, vc, ksc, vsc, bt, cl, cu, out, max_q_len, Hk, page, max_blocks, num_blocks, scale2,     \
-                       part_o, part_ml, num_splits);                                                               \
-    return (int)hipGetLastError()
-  switch (G) {
-    RCA_EXT(1);
-    RCA_EXT(2);
-    RCA_EXT(4);
-    RCA_EXT(8);
-  }
-#undef RCA_EXT
-  return -1;
-}
-
 }  // namespace
 
-// rca_attn_extend_paged_split (attention_extend.hip) over the fp8 cache: k_cache, v_cache = e4m3
-// bytes [num_blocks, page_size, Hk, D], k_scale, v_scale = fp32 [num_blocks, page_size, Hk]; every
-// other argument and check as there. num_splits == 1 is the unsplit launch: no workspace, T unread.
-RCA_API int rca_attn_extend_paged_fp8(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
-                                      const void* k_scale, const void* v_scale, const int* block_table,
-                                      const int* context_lens, const int* cu_q_lens, void* out, void* part_o,
-                                      void* part_ml, int B, long long T, int max_q_len, int Hq, int Hk, int D,
-                                      int page_size, int max_blocks, int num_blocks, float scale, int num_splits,
-                                      hipStream_t stream) {
-  if (B == 0 || max_q_len == 0) return 0;
-  if (B < 0 || max_q_len < 0 || Hq <= 0 || Hk <= 0 || Hq % Hk || (D != 64 && D != 128)) return -1;
-  if (page_size <= 0 || (page_size & 15) || max_blocks <= 0 || num_blocks <= 0 || !(scale > 0.f)) return -1;
-  if (q_stride < (long long)Hq * D || (q_stride & 7) || num_splits < 1 || (num_splits > 1 && T < 0)) return -1;
-  const int G = Hq / Hk;
-  const long long tiles = ((long long)max_q_len * G + 127) / 128 * num_splits;
-  if (B > 65535 || Hk > 65535 || tiles >= (1LL << 31) || (long long)num_blocks * page_size >= (1LL << 31)) return -2;
-  if (((uintptr_t)q | (uintptr_t)out) & 15) return -3;
-  if (((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) return -3;
-  if (!k_scale || !v_scale || (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3)) return -3;
-  if (num_splits > 1 && (!part_o || !part_ml || (((uintptr_t)part_o | (uintptr_t)part_ml) & 15))) return -3;
-  const float scale2 = scale * 1.44269504088896340736f;
-  const dim3 grid((unsigned)tiles, Hk, B);
-#define RCA_EXT_ARGS                                                                                    \
-  G, grid, stream, (const bf16_t*)q, (long)q_stride, (const fp8_t*)k_cache, (const fp8_t*)v_cache,      \
-      (const float*)k_scale, (const float*)v_scale, block_table, context_lens, cu_q_lens, (bf16_t*)out, \
-      max_q_len, Hk, page_size, max_blocks, num_blocks, scale2, (float*)part_o, (float*)part_ml, num_splits
-  if (num_splits == 1)
-    return D == 128 ? launch_extend_fp8_g<128, false>(RCA_EXT_ARGS) : launch_extend_fp8_g<64, false>(RCA_EXT_ARGS);
-  const int rc = D == 128 ? launch_extend_fp8_g<128, true>(RCA_EXT_ARGS) : launch_extend_fp8_g<64, true>(RCA_EXT_ARGS);
-#undef RCA_EXT_ARGS
-  if (rc != 0 || T == 0) return rc;
+// rca_attn_extend_paged (attention_extend.hip) over the e4m3 cache.
+int launch_attn_extend_fp8(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
+                           const void* k_scale, const void* v_scale, const int* block_table, const int* context_lens,
+                           const int* cu_q_lens, void* out, void* part_o, void* part_ml, int B, long long T,
+                           int max_q_len, int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
+                           float scale, int num_splits, unsigned tiles, hipStream_t stream) {
+  const int rc = with_bool(num_splits > 1, [&](auto split) {
+    return paged_kv::dispatch_dg(D, Hq / Hk, [&](auto d, auto g) {
+      hipLaunchKernelGGL((attn_extend_paged_fp8_kernel<d.value, g.value, split.value>), dim3(tiles, Hk, B),
+                         dim3(kThreads), 0, stream, (const bf16_t*)q, (long)q_stride, (const fp8_t*)k_cache,
+                         (const fp8_t*)v_cache, (const float*)k_scale, (const float*)v_scale, block_table,
+                         context_lens, cu_q_lens, (bf16_t*)out, max_q_len, Hk, page_size, max_blocks, num_blocks,
+                         scale * paged_kv::kLog2e, (float*)part_o, (float*)part_ml, num_splits);
+      return (int)hipGetLastError();
+    });
+  });
+  if (rc != 0 || num_splits == 1 || T == 0) return rc;
   return launch_split_combine((const float*)part_o, (const float*)part_ml, (bf16_t*)out, (long)T * Hq, num_splits, D,
                               stream);
 }

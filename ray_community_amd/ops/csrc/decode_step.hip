@@ -18,6 +18,7 @@
 // and then quantises as kv_cache_append_fp8_kernel does (the power-of-two scale rule and
 // v_cvt_pk_fp8_f32 on the exact quotient). No LDS, no atomics.
 #include "kv_fp8.h"
+#include "paged_kv.h"
 #include "rope_rotate.h"
 
 namespace {
@@ -96,52 +97,33 @@ __global__ __launch_bounds__(256) void rope_kv_append_decode_kernel(
   }
 }
 
-template <bool FP8>
-int launch(void* qkv, long long row_stride, const void* cs, int max_pos, const int* block_table,
-           const int* context_lens, int max_blocks, void* k_cache, void* v_cache, void* k_scale, void* v_scale, int B,
-           int Hq, int Hk, int D, int page_size, int num_blocks, hipStream_t stream) {
-  if (B == 0) return 0;
-  if (B < 0 || Hq <= 0 || Hk <= 0 || (D != 64 && D != 128) || (row_stride & 7)) return -1;
-  if (row_stride < (long long)(Hq + 2 * Hk) * D) return -1;
-  if (page_size <= 0 || max_blocks <= 0 || num_blocks <= 0 || max_pos <= 0) return -1;
-  if (!qkv || !cs || !block_table || !context_lens || !k_cache || !v_cache) return -3;
-  if (((uintptr_t)qkv | (uintptr_t)cs) & 15) return -3;
-  if (((uintptr_t)k_cache | (uintptr_t)v_cache) & (FP8 ? 7 : 15)) return -3;
-  if (FP8 && (!k_scale || !v_scale || (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3))) return -3;
-  const long long n = (long long)B * (Hq + 2 * Hk) * (D / 16);
-  const long long blocks = (n + 255) / 256;
-  if (n >= (1LL << 31)) return -2;
-#define RCA_LAUNCH(DD)                                                                                             \
-  hipLaunchKernelGGL((rope_kv_append_decode_kernel<DD, FP8>), dim3((unsigned)blocks), dim3(256), 0, stream,        \
-                     (bf16_t*)qkv, (long)row_stride, (const float2*)cs, max_pos, block_table, context_lens,        \
-                     max_blocks, page_size, num_blocks, k_cache, v_cache, (float*)k_scale, (float*)v_scale, B, Hq, \
-                     Hk)
-  if (D == 64) RCA_LAUNCH(64);
-  else RCA_LAUNCH(128);
-#undef RCA_LAUNCH
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 // qkv: [B, >= (Hq+2Hk)*D] bf16 with row stride `row_stride` elements (a multiple of 8), 16-B aligned;
 // cs: [max_pos, D/2] float2 (cos, sin), 16-B aligned; block_table: int32 [B, max_blocks];
-// context_lens: int32 [B], each sequence's length including this token; caches: bf16
-// [num_blocks, page_size, Hk, D], 16-B aligned. D is 64 or 128.
+// context_lens: int32 [B], each sequence's length including this token; caches and scales: either
+// kind (paged_kv.h). D is 64 or 128.
 RCA_API int rca_rope_kv_append_decode(void* qkv, long long row_stride, const void* cs, int max_pos,
                                       const int* block_table, const int* context_lens, int max_blocks, void* k_cache,
-                                      void* v_cache, int B, int Hq, int Hk, int D, int page_size, int num_blocks,
-                                      hipStream_t stream) {
-  return launch<false>(qkv, row_stride, cs, max_pos, block_table, context_lens, max_blocks, k_cache, v_cache, nullptr,
-                       nullptr, B, Hq, Hk, D, page_size, num_blocks, stream);
-}
-
-// The same over the fp8 cache: caches are e4m3 bytes [num_blocks, page_size, Hk, D] (8-B aligned),
-// k_scale / v_scale fp32 [num_blocks, page_size, Hk].
-RCA_API int rca_rope_kv_append_decode_fp8(void* qkv, long long row_stride, const void* cs, int max_pos,
-                                          const int* block_table, const int* context_lens, int max_blocks,
-                                          void* k_cache, void* v_cache, void* k_scale, void* v_scale, int B, int Hq,
-                                          int Hk, int D, int page_size, int num_blocks, hipStream_t stream) {
-  return launch<true>(qkv, row_stride, cs, max_pos, block_table, context_lens, max_blocks, k_cache, v_cache, k_scale,
-                      v_scale, B, Hq, Hk, D, page_size, num_blocks, stream);
+                                      void* v_cache, void* k_scale, void* v_scale, int B, int Hq, int Hk, int D,
+                                      int page_size, int num_blocks, hipStream_t stream) {
+  if (B == 0) return 0;
+  if (B < 0 || !paged_kv::heads_ok(Hq, Hk) || (D != 64 && D != 128) || max_pos <= 0) return -1;
+  if (!paged_kv::rows_ok(row_stride, (long long)(Hq + 2 * Hk) * D)) return -1;
+  if (!paged_kv::pages_ok(page_size, max_blocks, num_blocks)) return -1;
+  const long long n = (long long)B * (Hq + 2 * Hk) * (D / 16);
+  if (n >= (1LL << 31)) return -2;
+  if (!paged_kv::all_set(qkv, cs, block_table, context_lens) || !paged_kv::aligned(16, qkv, cs)) return -3;
+  if (!paged_kv::caches_ok(k_cache, v_cache, k_scale, v_scale)) return -3;
+  auto launch = [&](auto fp8, auto d) {
+    hipLaunchKernelGGL((rope_kv_append_decode_kernel<d.value, fp8.value>), dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), 0, stream, (bf16_t*)qkv, (long)row_stride, (const float2*)cs, max_pos, block_table,
+                       context_lens, max_blocks, page_size, num_blocks, k_cache, v_cache, (float*)k_scale,
+                       (float*)v_scale, B, Hq, Hk);
+    return (int)hipGetLastError();
+  };
+  // bf16 before fp8 and 64 before 128: the kernels are emitted in the order they are named here
+  using paged_kv::int_c;
+  if (!k_scale) return D == 64 ? launch(std::false_type{}, int_c<64>{}) : launch(std::false_type{}, int_c<128>{});
+  return D == 64 ? launch(std::true_type{}, int_c<64>{}) : launch(std::true_type{}, int_c<128>{});
 }
