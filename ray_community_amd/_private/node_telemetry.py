@@ -6,7 +6,9 @@ Sources, cheapest first, none of which initialises HIP in the reporting process:
 
   * AMD GPU sysfs (``/sys/class/drm/cardN/device``): ``mem_info_vram_used`` / ``_total`` (HBM
     bytes), ``gpu_busy_percent``, ``pp_dpm_sclk`` (current shader clock), hwmon ``power1_average``
-    / ``power1_input`` (uW) and ``temp*_input`` (m degC, labelled edge / junction / mem);
+    / ``power1_input`` (uW) and ``temp*_input`` (m degC, labelled edge / junction / mem); where
+    a card's ``mem_info_vram_used`` is missing (seen in virtual machines) the same counter is
+    read from the amdgpu driver by an ``AMDGPU_INFO`` ioctl on the card's render node;
   * ``amd-smi metric --json`` (``parse_amd_smi_metric``) when sysfs is not readable, e.g. inside
     containers that hide it; its JSON layout differs across ROCm releases (a bare list, or
     ``{"gpu_data": [...]}``; values as numbers, ``{"value", "unit"}`` dicts or "123 W" strings),
@@ -61,6 +63,35 @@ def _current_sclk(text: Optional[str]) -> Optional[float]:
     return None
 
 
+# DRM_IOCTL_AMDGPU_INFO = _IOW('d', DRM_COMMAND_BASE + DRM_AMDGPU_INFO, struct drm_amdgpu_info)
+# (include/uapi/drm/amdgpu_drm.h): {u64 return_pointer; u32 return_size; u32 query; 16 bytes of
+# per-query arguments}; query AMDGPU_INFO_VRAM_USAGE returns one u64, the bytes of VRAM in use
+_DRM_IOCTL_AMDGPU_INFO = 0x40206445
+_AMDGPU_INFO_VRAM_USAGE = 0x10
+
+
+def _drm_vram_used(render_node: str) -> Optional[int]:
+    """Used VRAM in bytes from the amdgpu driver through the GPU's render node: the counter behind
+    sysfs ``mem_info_vram_used``, for hosts (virtual machines) whose sysfs lacks that file. One
+    ioctl on ``/dev/dri/renderD*``: no fork, no HIP context."""
+    import ctypes
+    import fcntl
+    import struct
+
+    try:
+        fd = os.open(render_node, os.O_RDWR)
+    except OSError:
+        return None
+    try:
+        v = ctypes.c_uint64(0)
+        fcntl.ioctl(fd, _DRM_IOCTL_AMDGPU_INFO, struct.pack("QII16x", ctypes.addressof(v), 8, _AMDGPU_INFO_VRAM_USAGE))
+        return int(v.value)
+    except OSError:
+        return None
+    finally:
+        os.close(fd)
+
+
 def read_gpus_sysfs(root: str = _SYSFS_ROOT) -> List[Dict]:
     cards = []
     for p in glob.glob(os.path.join(root, "card*")):
@@ -81,6 +112,9 @@ def read_gpus_sysfs(root: str = _SYSFS_ROOT) -> List[Dict]:
                "busy_percent": _read_int(os.path.join(d, "gpu_busy_percent")),
                "sclk_mhz": _current_sclk(_read(os.path.join(d, "pp_dpm_sclk"))),
                "power_w": None, "temp_c": {}}
+        if rec["vram_used"] is None:
+            for rn in glob.glob(os.path.join(d, "drm", "renderD*"))[:1]:  # a card has one render node
+                rec["vram_used"] = _drm_vram_used(os.path.join("/dev/dri", os.path.basename(rn)))
         for h in sorted(glob.glob(os.path.join(d, "hwmon", "hwmon*"))):
             pw = _read_int(os.path.join(h, "power1_average"))
             if pw is None:

@@ -31,6 +31,7 @@ __all__ = [
     "standardize_", "gbdt_histogram",
     "batched_concat",
     "image_normalize",
+    "graph_memsets_to_kernels",
     "crop_resize_normalize",
     "batch_norm_act",
     "flash_attention",
@@ -737,6 +738,19 @@ def image_normalize(u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), d
                                     ctypes.cast(sa, ctypes.c_void_p), 0 if dtype == torch.bfloat16 else 1,
                                     1 if channels_last else 0, stream_ptr(u8.device)), "image_normalize")
     return out
+
+
+def graph_memsets_to_kernels(graph) -> int:
+    """Rewrite the memset nodes of a captured ``torch.cuda.CUDAGraph(keep_graph=True)`` into HIP
+    fill-kernel nodes (same bytes, same place in the graph), before it is instantiated; returns
+    how many. Library code inside a capture (PyTorch's reductions, MIOpen) records
+    ``hipMemsetAsync`` calls as memset nodes, which some hosts execute in the first replay only
+    (``csrc/graph_memset.hip``)."""
+    import ctypes
+
+    n = ctypes.c_int(0)
+    check(lib().rca_graph_memsets_to_kernels(graph.raw_cuda_graph(), ctypes.byref(n)), "graph_memsets_to_kernels")
+    return n.value
 
 
 def crop_resize_normalize(u8, boxes, size, flips=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),

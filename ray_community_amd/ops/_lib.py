@@ -80,6 +80,7 @@ _SIGS = {
                               c_void_p]),
     "rca_image_normalize": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                      c_void_p]),
+    "rca_graph_memsets_to_kernels": (c_int, [c_void_p, c_void_p]),  # hipGraph_t, int* replaced
     "rca_kv_cache_append": (c_int, [c_void_p, c_ll, c_void_p, *_KV,  # qkv, row_stride, slot_mapping
         c_ll, c_int, c_int, c_int, c_ll, c_void_p]),  # T, Hq, Hk, D, num_slots, stream
     "rca_rope_kv_append_decode": (c_int, [c_void_p, c_ll, c_void_p, c_int,  # qkv, row_stride, cs, max_pos

@@ -743,9 +743,15 @@ class _PPOStepGraph:
             self.warm += 1
             return
         lr.opt.zero_grad(set_to_none=True)
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.cuda.graph(graph):
             self._body(lr)
+        # the conv module's capture holds memset nodes (the semaphores of PyTorch's bias-gradient
+        # reductions, the output of MIOpen's backward-data convolutions), which some hosts run
+        # in a graph's first replay only (csrc/graph_memset.hip): the step then drifts from the
+        # eager loop from the second update on. Replay them as fill kernels.
+        ops.graph_memsets_to_kernels(graph)
+        graph.instantiate()
         self.graph = graph
         graph.replay()  # the capture recorded this minibatch's step without running it
         self.replays += 1

@@ -42,6 +42,23 @@ def test_sysfs_reader(tmp_path):
     assert r["temp_c"] == {"edge": 45.0, "junction": 61.0}
 
 
+def test_sysfs_reader_used_vram_from_render_node(tmp_path, monkeypatch):
+    """A card whose sysfs has no mem_info_vram_used (virtual machines): the used bytes come from
+    the amdgpu driver through the card's own render node; a card that has the file is not asked."""
+    for i, used in enumerate([None, 3 << 30]):
+        d = tmp_path / f"card{i}" / "device"
+        _w(str(d / "mem_info_vram_total"), str(288 << 30))
+        if used is not None:
+            _w(str(d / "mem_info_vram_used"), str(used))
+        _w(str(d / "drm" / f"renderD{128 + i}" / "dev"), f"226:{128 + i}")
+    assert nt._drm_vram_used(str(tmp_path / "no_such_node")) is None  # unreadable: reported as unknown
+    asked = []
+    monkeypatch.setattr(nt, "_drm_vram_used", lambda node: asked.append(node) or 5 << 30)
+    g = nt.read_gpus_sysfs(str(tmp_path))
+    assert [r["vram_used"] for r in g] == [5 << 30, 3 << 30]
+    assert asked == ["/dev/dri/renderD128"]
+
+
 _AMD_SMI_DICT_VALUES = [{
     "gpu": 0,
     "usage": {"gfx_activity": {"value": 93, "unit": "%"}, "umc_activity": {"value": 40, "unit": "%"}},
