@@ -172,8 +172,10 @@ class Llama(nn.Module):
 
     def quantize_weights_(self, dtype="fp8"):
         """Quantise the linears' weights in place for inference (``models/quant.py``): ``"fp8"``
-        halves their bytes; ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run
-        ``ops.linear_w8``. Idempotent. Training paths are not available afterwards."""
+        halves their bytes and ``"mxfp4"`` (OCP microscaling FP4, 4.25 bits a weight) nearly halves
+        them again; ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run
+        ``ops.linear_w8`` / ``ops.linear_w4``. Idempotent for the same format; the other format
+        raises ``RuntimeError``. Training paths are not available afterwards."""
         self.module_epoch += 1
         return quantize_weights_(self, dtype)
 
@@ -546,8 +548,8 @@ from .decoding import _seeded_generator, sample_tokens, use_fused_sampling  # no
 
 
 def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, weight_dtype=None, **overrides) -> Llama:
-    """``weight_dtype``: ``None`` / ``"auto"`` keep the linears in ``dtype``; ``"fp8"`` quantises them
-    (``Llama.quantize_weights_``) after the cast."""
+    """``weight_dtype``: ``None`` / ``"auto"`` keep the linears in ``dtype``; ``"fp8"`` / ``"mxfp4"`` quantise
+    them (``Llama.quantize_weights_``) after the cast."""
     cfg = PRESETS[name_or_cfg] if isinstance(name_or_cfg, str) else name_or_cfg
     if overrides:
         cfg = LlamaConfig(**{**cfg.__dict__, **overrides})

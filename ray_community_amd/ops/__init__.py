@@ -51,6 +51,9 @@ __all__ = [
     "linear_w8",
     "linear_w8_supported",
     "dequant_w8",
+    "linear_w4",
+    "linear_w4_supported",
+    "dequant_w4",
     "lora_routing",
     "lora_supported",
     "lora_add_",
@@ -1710,6 +1713,105 @@ def linear_w8(x, qweight, scale, out=None):
             return out
     else:
         w = dequant_w8(qweight, scale, _workspace(x.device, "linear_w8_dequant", N * K, torch.bfloat16)[:N * K].view(N, K))
+        y = torch.nn.functional.linear(x2, w)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y.view(*lead, N)
+
+
+# ----------------------------------------------------------------------------------- MXFP4 weights
+# Rows up to which ``linear_w4`` runs the W4A16 kernel (ops/csrc/linear_w4.hip); above it the weight is
+# dequantised into a workspace and the product is a bf16 ``F.linear``. 32 is the kernel's single-pass
+# row tile (one stream of the weight) and the largest measured M at which the kernel beats the bf16 arm
+# on every llama3-8b shape (at M = 64 it loses on gate_up): profiles/weight_mxfp4.md.
+M_SKINNY_W4 = 32
+
+
+def _w4_tensor_ok(t) -> bool:
+    return torch.is_tensor(t) and t.dtype in (torch.bfloat16, torch.uint8) and _w8_tensor_ok(t)
+
+
+def linear_w4_supported(M: int, N: int, K: int, *tensors) -> bool:
+    """What the W4A16 kernel takes: ``K % 256 == 0``, ``N % 16 == 0``, ``M >= 1``; CUDA tensors with
+    16-byte aligned bases: bf16 2-D ``x`` / ``out`` with unit inner stride and a row stride that is
+    a multiple of 8, contiguous uint8 ``[N, K/2]`` nibble pairs and ``[N, K/32]`` E8M0 scales."""
+    return M >= 1 and N > 0 and K > 0 and N % 16 == 0 and K % 256 == 0 and all(_w4_tensor_ok(t) for t in tensors)
+
+
+def _linear_w4_kernel(x2, qweight, scale, out):
+    """The kernel launch on operands ``linear_w4_supported`` accepts, whatever M is."""
+    M, K = x2.shape
+    N = qweight.shape[0]
+    L = lib()
+    splits = L.rca_linear_w4_splits(N, K)
+    ws = _workspace(x2.device, "linear_w4_split", splits * M * N) if splits > 1 else None
+    check(L.rca_linear_w4a16(x2.data_ptr(), qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), _p(ws),
+                             ws.numel() * 4 if ws is not None else 0, M, N, K, x2.stride(0), out.stride(0),
+                             stream_ptr(x2.device)), "linear_w4a16")
+    return out
+
+
+def _check_w4(name, qweight, scale):
+    if qweight.dtype != torch.uint8 or scale.dtype != torch.uint8 or qweight.dim() != 2 or qweight.shape[1] % 16 \
+            or tuple(scale.shape) != (qweight.shape[0], qweight.shape[1] // 16):
+        raise ValueError(f"{name}: qweight must be uint8 [N, K/2] with K % 32 == 0 and scale uint8 [N, K/32], got "
+                         f"{tuple(qweight.shape)} {qweight.dtype} and {tuple(scale.shape)} {scale.dtype}")
+    return qweight.shape[0], qweight.shape[1] * 2
+
+
+def dequant_w4(qweight, scale, out=None):
+    """``qweight [N, K/2]`` (e2m1 nibble pairs) times ``2^(scale - 127)`` (``scale [N, K/32]`` E8M0
+    bytes) as bf16 ``[N, K]``: exact. GPU: one vectorised kernel; CPU:
+    ``reference.dequantize_mxfp4_ref``."""
+    N, K = _check_w4("dequant_w4", qweight, scale)
+    if not (_w4_tensor_ok(qweight) and _w4_tensor_ok(scale)):
+        w = ref.dequantize_mxfp4_ref(qweight, scale)
+        return w if out is None else out.copy_(w)
+    if out is None:
+        out = torch.empty((N, K), device=qweight.device, dtype=torch.bfloat16)
+    elif not (out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (N, K)
+              and out.data_ptr() % 16 == 0):
+        raise ValueError("dequant_w4: out must be a contiguous, 16-byte aligned bf16 [N, K] CUDA tensor")
+    check(lib().rca_dequant_w4(qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), N, K, stream_ptr(out.device)),
+          "dequant_w4")
+    return out
+
+
+def linear_w4(x, qweight, scale, out=None):
+    """``x [..., K] @ deq(qweight, scale).T`` for an MXFP4-quantised weight
+    (``reference.quantize_weight_mxfp4_ref``: ``uint8 [N, K/2]`` e2m1 nibble pairs, the low nibble the
+    even ``k``, and ``uint8 [N, K/32]`` E8M0 block scales, any value in ``[2, 252]``). No autograd:
+    inference only.
+
+    bf16 CUDA ``x`` within ``linear_w4_supported``: up to ``M_SKINNY_W4`` rows run the W4A16 kernel
+    (the weight is streamed as nibbles, converted to bf16 in registers with its block scale applied,
+    accumulated in fp32 on the MFMA and rounded once; an output row depends on its own input row
+    only, not on the batch it came in). More rows (prefill) dequantise the weight into one
+    per-device bf16 workspace on the current stream and call ``F.linear``. An ``x`` with a non-unit
+    inner stride or a misaligned base is made contiguous first. CPU tensors, other dtypes and shapes
+    outside the contract run ``reference.linear_w4_ref``. ``out``: a bf16 ``[M, N]`` tensor or view
+    to write."""
+    N, K = _check_w4("linear_w4", qweight, scale)
+    if x.shape[-1] != K:
+        raise ValueError(f"linear_w4: x [..., {x.shape[-1]}] and qweight [{N}, {K}/2] do not agree")
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, K)
+    M = x2.shape[0]
+    if out is not None and (tuple(out.shape) != (M, N) or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError(f"linear_w4: out must be a {x.dtype} [{M}, {N}] tensor on {x.device}")
+    if x2.is_cuda and x2.dtype == torch.bfloat16 and not _w8_tensor_ok(x2):
+        x2 = x2.contiguous()
+    if not linear_w4_supported(M, N, K, x2, qweight, scale):
+        y = ref.linear_w4_ref(x2, qweight, scale)
+    elif M <= M_SKINNY_W4:
+        direct = out is not None and _w4_tensor_ok(out)
+        y = _linear_w4_kernel(x2, qweight, scale,
+                              out if direct else torch.empty((M, N), device=x.device, dtype=torch.bfloat16))
+        if direct:
+            return out
+    else:
+        w = dequant_w4(qweight, scale, _workspace(x.device, "linear_w4_dequant", N * K, torch.bfloat16)[:N * K].view(N, K))
         y = torch.nn.functional.linear(x2, w)
     if out is not None:
         out.copy_(y)

@@ -30,7 +30,8 @@ EXTRA_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 _ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # no v_pk_{add,mul,fma}_f32
 FILE_FLAGS = {"attention_dkdv.hip": _ILP, "attention_fwd_wide.hip": _ILP, "attention_fwd_hs.hip": _ILP, "gemm4.hip": [],
-              "attention.hip": EXTRA_FLAGS + _ILP, "graph_memset.hip": EXTRA_FLAGS + _NO_PK_F32}
+              "attention.hip": EXTRA_FLAGS + _ILP, "graph_memset.hip": EXTRA_FLAGS + _NO_PK_F32,
+              "linear_w4.hip": EXTRA_FLAGS + _NO_PK_F32}
 
 
 def _hipcc() -> str:

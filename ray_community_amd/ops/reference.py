@@ -201,6 +201,53 @@ def linear_w8_ref(x, qweight, scale):
     return torch.nn.functional.linear(x, kv_dequantize_fp8_ref(qweight, scale, x.dtype))
 
 
+MXFP4_BLOCK = 32  # k per E8M0 scale byte (OCP microscaling)
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # |e2m1| by its three low bits; bit 3 is the sign
+
+
+def quantize_weight_mxfp4_ref(w):
+    """Quantise a linear's weight ``[N, K]`` to OCP MXFP4: returns ``(q [N, K/2] uint8, e [N, K/32]
+    uint8)``. A byte of ``q`` holds two e2m1 nibbles, the low one the even ``k``; ``e`` is one E8M0
+    byte per 32 consecutive ``k`` of a row, the block scale ``2^(e - 127)``. The scale of a block is
+    the smallest power of two ``s`` with ``max|w| / s <= 6``, ``e = 127`` for an all-zero block and
+    ``e`` clamped to ``[2, 252]`` so that every nonzero product is a normal bf16; the stored element
+    is the round-to-nearest-even e2m1 of ``w / s`` (at most 6, so nothing saturates short of the
+    clamp). ``K % 32 != 0`` or a weight that is not 2-D raises ``ValueError``."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError("quantize_weight_mxfp4_ref: weight must be [N, K] with K % 32 == 0")
+    N, K = w.shape
+    wf = w.float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=-1)
+    mant, exp = torch.frexp(amax)  # amax = mant * 2^exp, mant in [0.5, 1); 6 = 0.75 * 2^3
+    e = exp - 3 + (mant > 0.75).to(exp.dtype) + 127
+    e = torch.where(amax == 0, torch.full_like(e, 127), e.clamp(2, 252))
+    scale = (e.to(torch.int32) << 23).view(torch.float32)
+    a = (wf / scale.unsqueeze(-1)).abs().clamp(max=6.0)
+    # e2m1 steps: 0.5 below 2, 1 below 4, 2 above; torch.round is half-to-even, which is the even code
+    r = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    code = torch.where(r <= 2, r * 2, torch.where(r <= 4, r + 2, torch.full_like(r, 7))).to(torch.uint8)
+    code = (code | (((wf < 0) & (r > 0)).to(torch.uint8) << 3)).view(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), e.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4_ref(q, e, dtype=torch.bfloat16):
+    """``q [N, K/2]`` e2m1 pairs times ``2^(e - 127)`` (``e [N, K/32]``) as ``[N, K]`` in ``dtype``:
+    a 16-entry table times the scale, exact in bf16, fp32 and fp64 for ``2 <= e <= 252``."""
+    N, K = q.shape[0], q.shape[1] * 2
+    if q.dtype != torch.uint8 or e.dtype != torch.uint8 or tuple(e.shape) != (N, K // MXFP4_BLOCK) or K % MXFP4_BLOCK:
+        raise ValueError(f"dequantize_mxfp4_ref: q {tuple(q.shape)} and e {tuple(e.shape)} must be uint8 [N, K/2], [N, K/32]")
+    table = torch.tensor(MXFP4_VALUES + tuple(-v for v in MXFP4_VALUES), dtype=torch.float32, device=q.device)
+    vals = table[torch.stack((q & 0xF, q >> 4), dim=-1).long()].view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    scale = (e.to(torch.int32) << 23).view(torch.float32)
+    return (vals * scale.unsqueeze(-1)).view(N, K).to(dtype)
+
+
+def linear_w4_ref(x, qweight, scale):
+    """``x [..., K] @ dequantize_mxfp4_ref(qweight, scale).T`` with the weight dequantised (exactly)
+    to ``x.dtype``: the reference of ``ops.linear_w4``."""
+    return torch.nn.functional.linear(x, dequantize_mxfp4_ref(qweight, scale, x.dtype))
+
+
 def lora_add_ref(y, x, A, B, scale, idx):
     """Per-row LoRA update, in place on ``y [M, N]``: with ``a = idx[m] >= 0`` the adapter slot of row
     ``m`` (``A [S, R, K]``, ``B [S, N, R]``, ``scale [S]`` fp32),

@@ -33,9 +33,10 @@ class _LlamaDeployment:
         one forward (``GenerationEngine(speculative=...)``; implies ``fused_sampling``);
         ``num_blocks`` (default 256) or ``cache_bytes`` size the KV cache and ``kv_cache_dtype``
         (``"fp8"``: quantised pages, about half the bytes per token) picks its dtype, as in
-        ``GenerationEngine``; ``weight_dtype`` (``None`` / ``"auto"`` / ``"fp8"``): ``"fp8"`` quantises
-        the linears' weights once the state dict is loaded (``Llama.quantize_weights_``: half the
-        weight bytes, activations stay in ``dtype``); ``lora={"max_adapters": n, "max_rank": r}``
+        ``GenerationEngine``; ``weight_dtype`` (``None`` / ``"auto"`` / ``"fp8"`` / ``"mxfp4"``): ``"fp8"`` and
+        ``"mxfp4"`` quantise the linears' weights once the state dict is loaded
+        (``Llama.quantize_weights_``: a half and about a quarter of the bf16 weight bytes,
+        activations stay in ``dtype``); ``lora={"max_adapters": n, "max_rank": r}``
         makes room for LoRA adapters (``Llama.enable_lora_``, after the quantisation) that requests
         select by name, and ``adapters={"name": path}`` preloads ``LoraAdapter.save``d files;
         ``graph_decode``: the engine replays its decode step as a captured HIP graph
@@ -58,7 +59,7 @@ class _LlamaDeployment:
         for name, path in (adapters or {}).items():
             self.model.load_adapter(name, LoraAdapter.load(path))
         self.model.eval()
-        self.weight_dtype = "fp8" if weight_dtype == "fp8" else None
+        self.weight_dtype = weight_dtype if weight_dtype in ("fp8", "mxfp4") else None
         self.weight_bytes = weight_bytes(self.model)
         self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
                                        prefill_chunk=prefill_chunk, fused_sampling=fused_sampling,
@@ -167,7 +168,7 @@ class _LlamaDeployment:
         their prompt), one with ``fused_sampling`` adds ``"fused_sampling": True``, one with
         ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``, one with an fp8
         cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``, one with fp8
-        weights adds ``"weight_dtype": "fp8"`` and ``"weight_bytes"`` (the model's parameters and buffers),
+        or mxfp4 weights adds ``"weight_dtype": "fp8"`` / ``"mxfp4"`` and ``"weight_bytes"`` (the model's parameters and buffers),
         one with ``lora`` adds ``"lora": {"max_adapters", "max_rank", "loaded": [...], "bank_bytes"}``,
         one with ``graph_decode`` adds ``"graph_decode": {"graphs", "replays", "eager_warm", "eager_fallback"}``."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}

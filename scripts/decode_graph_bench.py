@@ -15,6 +15,7 @@ Op: ``ops.rope_kv_append_decode_`` against ``apply_rope_`` + ``kv_cache_append_`
 at B = 1 and 32, bf16 and fp8 cache, device events, medians (us).
 
     python scripts/decode_graph_bench.py [--models llama3-1b,llama3-8b] [--batches 1,8,32] [--json out.json]
+                                         [--weights bf16,fp8,mxfp4]
 """
 import argparse
 import json
@@ -85,11 +86,11 @@ def _wall(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3  # ms
 
 
-def model_bench(name, batches, new_tokens, prompt_len, reps, steps):
+def model_bench(name, batches, new_tokens, prompt_len, reps, steps, weight_dtypes=("bf16", "fp8")):
     rows = []
-    for weights, kv_dtype in (("bf16", None), ("fp8", None), ("bf16", "fp8")):
+    for weights, kv_dtype in [(w, None) for w in weight_dtypes] + [("bf16", "fp8")]:
         torch.manual_seed(0)
-        model = build_llama(name, device="cuda", weight_dtype=weights if weights == "fp8" else None).eval()
+        model = build_llama(name, device="cuda", weight_dtype=None if weights == "bf16" else weights).eval()
         page = 16
         for B in batches:
             g = torch.Generator().manual_seed(B)
@@ -156,6 +157,7 @@ def main():
     ap.add_argument("--no-op", action="store_true")
     ap.add_argument("--no-generate", action="store_true")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--weights", default="bf16,fp8", help="weight dtypes of the generate arms: bf16, fp8, mxfp4")
     args = ap.parse_args()
     result = {"device": torch.cuda.get_device_name(0), "op": [], "generate": []}
     if not args.no_op:
@@ -163,7 +165,7 @@ def main():
     if not args.no_generate:
         for name in args.models.split(","):
             result["generate"] += model_bench(name, [int(b) for b in args.batches.split(",")], args.new_tokens,
-                                              args.prompt_len, args.reps, args.steps)
+                                              args.prompt_len, args.reps, args.steps, args.weights.split(","))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(result, f, indent=1)
