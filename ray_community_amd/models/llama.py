@@ -46,6 +46,8 @@ class LlamaConfig:
     attn_impl: str = "hip"  # "hip" (gfx950 flash attention kernels) | "sdpa" (torch SDPA / aotriton)
     fused_ce: bool = False  # chunked lm_head + one-pass HIP CE (parallel/fused_linear.py): no T x V logits
     ce_chunk: int = 0       # tokens per fused-CE chunk (0: <= 1 GiB of logits per chunk)
+    num_experts: int = 0        # 0: the dense MLP; E >= 2: a router and E expert MLPs per block (MoEMLP)
+    experts_per_token: int = 2  # experts a token is routed to
 
     @property
     def head_dim(self) -> int:
@@ -54,7 +56,8 @@ class LlamaConfig:
     def num_params(self) -> int:
         H, I, V, L = self.hidden_size, self.intermediate_size, self.vocab_size, self.num_layers
         kv = self.num_kv_heads * self.head_dim
-        per_layer = H * (H + 2 * kv) + H * H + 2 * H * I + I * H + 2 * H
+        mlp = 3 * H * I if not self.num_experts else self.num_experts * (3 * H * I + H)  # + the router's rows
+        per_layer = H * (H + 2 * kv) + H * H + mlp + 2 * H
         emb = V * H * (1 if self.tie_embeddings else 2)
         return L * per_layer + emb + H
 
@@ -62,6 +65,8 @@ class LlamaConfig:
         """Training FLOPs/token: 6 * matmul params + causal attention (fwd+bwd)."""
         H, L = self.hidden_size, self.num_layers
         n_matmul = self.num_params() - self.vocab_size * H * (0 if self.tie_embeddings else 1) - (2 * L + 1) * H
+        if self.num_experts:  # the router and the experts_per_token active experts
+            n_matmul -= L * (self.num_experts - self.experts_per_token) * 3 * H * self.intermediate_size
         attn = 6 * L * H * seq_len  # 12*L*H*S/2 (causal): QK^T + PV, fwd + 2x bwd
         return 6 * n_matmul + attn
 
@@ -74,6 +79,11 @@ PRESETS = {
                              tie_embeddings=True, name="llama3-1b"),
     "llama3-tiny": LlamaConfig(vocab_size=1024, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=4,
                                num_kv_heads=2, max_seq_len=256, name="llama3-tiny"),
+    "mixtral-8x7b": LlamaConfig(vocab_size=32000, hidden_size=4096, intermediate_size=14336, num_layers=32, num_heads=32,
+                                num_kv_heads=8, max_seq_len=32768, rope_theta=1e6, num_experts=8, experts_per_token=2,
+                                name="mixtral-8x7b"),
+    "mixtral-tiny": LlamaConfig(vocab_size=1024, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=4,
+                                num_kv_heads=2, max_seq_len=256, num_experts=4, experts_per_token=2, name="mixtral-tiny"),
 }
 
 
@@ -133,13 +143,39 @@ class MLP(nn.Module):
         return swiglu_down(self.gate_up(x), self.down)
 
 
+class MoEMLP(nn.Module):
+    """Sparse mixture of experts in place of the MLP (Mixtral): a router picks ``experts_per_token`` of
+    ``num_experts`` SwiGLU MLPs per token and the block's output is their softmax-weighted sum.
+    ``router.weight [E, H]``, ``w_gate_up [E, 2I, H]`` (gate rows, then up rows: the dense fused order)
+    and ``w_down [E, H, I]``. Inference runs ``ops.moe_route`` and ``ops.moe_ffn``; under autograd the
+    differentiable torch reference runs (no load-balancing loss)."""
+
+    def __init__(self, cfg: LlamaConfig):
+        super().__init__()
+        E, H, I = cfg.num_experts, cfg.hidden_size, cfg.intermediate_size
+        if E < 2 or not 1 <= cfg.experts_per_token <= E:
+            raise ValueError(f"MoEMLP needs num_experts >= 2 and 1 <= experts_per_token <= num_experts, got "
+                             f"{E} and {cfg.experts_per_token}")
+        self.top_k = cfg.experts_per_token
+        self.router = nn.Linear(H, E, bias=False)
+        self.w_gate_up = nn.Parameter(torch.empty(E, 2 * I, H))
+        self.w_down = nn.Parameter(torch.empty(E, H, I))
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or self.w_down.requires_grad):
+            ids, weights = ops.reference.moe_route_ref(x, self.router.weight, self.top_k)
+            return ops.reference.moe_ffn_ref(x, ids, weights, self.w_gate_up, self.w_down)
+        ids, weights = ops.moe_route(x, self.router.weight, self.top_k)
+        return ops.moe_ffn(x, ids, weights, self.w_gate_up, self.w_down)
+
+
 class Block(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         self.attn_norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
         self.attn = Attention(cfg)
         self.mlp_norm = RMSNorm(cfg.hidden_size, cfg.norm_eps)
-        self.mlp = MLP(cfg)
+        self.mlp = MoEMLP(cfg) if cfg.num_experts else MLP(cfg)
 
 
 class Llama(nn.Module):
@@ -165,7 +201,7 @@ class Llama(nn.Module):
         for name, p in self.named_parameters():
             if p.dim() == 1:
                 p.fill_(1.0)
-            elif name.endswith("o.weight") or name.endswith("down.weight"):
+            elif name.endswith("o.weight") or name.endswith("down.weight") or name.endswith("mlp.w_down"):
                 p.normal_(0.0, out_std)
             else:
                 p.normal_(0.0, std)
@@ -176,6 +212,8 @@ class Llama(nn.Module):
         them again; ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run
         ``ops.linear_w8`` / ``ops.linear_w4``. Idempotent for the same format; the other format
         raises ``RuntimeError``. Training paths are not available afterwards."""
+        if self.cfg.num_experts and dtype in ("fp8", "mxfp4"):
+            raise NotImplementedError("quantised expert weights are not implemented for MoE models")
         self.module_epoch += 1
         return quantize_weights_(self, dtype)
 
@@ -185,6 +223,8 @@ class Llama(nn.Module):
         ``LoraLinear``s around their base modules (before or after ``quantize_weights_``), and
         ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` take ``adapters=``. With no adapter
         named every logit keeps its bits. Training paths are not available afterwards."""
+        if self.cfg.num_experts:
+            raise NotImplementedError("LoRA is not implemented for MoE models")
         self.module_epoch += 1
         return _lora.enable_lora_(self, max_adapters, max_rank)
 

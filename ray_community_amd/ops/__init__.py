@@ -57,6 +57,9 @@ __all__ = [
     "lora_routing",
     "lora_supported",
     "lora_add_",
+    "moe_route",
+    "moe_ffn",
+    "moe_supported",
     "kernels_available",
 ]
 
@@ -1922,3 +1925,114 @@ def lora_add_(y, x, A, B, scale, routing):
     if lora_supported(M, N, K, R, y, x, A, B, scale) and routing.idx.device == y.device:
         return _lora_kernel(y, x, A, B, scale, routing)
     return ref.lora_add_ref(y, x, A, B, scale, routing.idx)
+
+
+# ----------------------------------------------------------------------------------- mixture of experts
+# Rows up to which ``moe_ffn`` runs the grouped expert kernels (ops/csrc/moe.hip); above it the pairs
+# are sorted by expert and every expert runs two bf16 ``F.linear``s over its rows (one host read of the
+# counts). The largest power-of-two T at which the kernels beat that arm at the mixtral-8x7b layer
+# shape in the same process: profiles/moe.md has the table.
+M_MOE = 64
+MOE_MAX_EXPERTS = 64   # an expert's logit lives in its lane
+MOE_MAX_TOP_K = 8
+
+
+def _moe_tensor_ok(t) -> bool:
+    if not (torch.is_tensor(t) and t.is_cuda and t.data_ptr() % 16 == 0):
+        return False
+    if t.dtype in (torch.int32, torch.float32):  # ids / weights
+        return t.dim() == 2 and t.is_contiguous()
+    if t.dtype != torch.bfloat16:
+        return False
+    if t.dim() == 3:  # the expert weights
+        return t.is_contiguous()
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.shape[1]  # x / y views
+
+
+def moe_supported(T: int, H: int, I: int, E: int, k: int, *tensors) -> bool:
+    """What the MoE kernels take: ``H % 128 == 0``, ``I % 128 == 0``, ``T >= 1``, ``2 <= E <= 64``,
+    ``1 <= k <= min(E, 8)``; CUDA tensors with 16-byte aligned bases: bf16 2-D ``x`` / ``y`` with unit
+    inner stride and a row stride that is a multiple of 8, contiguous bf16 weights, contiguous int32
+    ``ids`` and fp32 ``weights``. A tensor is judged by its own dtype here; which operand must be bf16 is
+    checked by ``moe_route`` and ``moe_ffn``, so fp32 activations or expert weights on the GPU run the reference."""
+    return (T >= 1 and H > 0 and I > 0 and H % 128 == 0 and I % 128 == 0 and 2 <= E <= MOE_MAX_EXPERTS
+            and 1 <= k <= min(E, MOE_MAX_TOP_K) and all(_moe_tensor_ok(t) for t in tensors))
+
+
+def moe_route(x, w_router, k: int):
+    """Top-``k`` expert routing of ``x [T, H]`` with the router weight ``w_router [E, H]``: ``(ids int32
+    [T, k], weights fp32 [T, k])``, the ``k`` largest router logits in descending order (equal logits by
+    ascending expert) and their softmax (``reference.moe_route_ref``). bf16 CUDA operands within
+    ``moe_supported`` run one gfx950 kernel, a wave per row, with no host read; everything else runs the
+    reference."""
+    if x.dim() != 2 or w_router.dim() != 2 or x.shape[1] != w_router.shape[1]:
+        raise ValueError(f"moe_route: x {tuple(x.shape)} and w_router {tuple(w_router.shape)} do not agree")
+    (T, H), E, k = x.shape, w_router.shape[0], int(k)
+    if not 1 <= k <= E:
+        raise ValueError(f"moe_route: k must be in [1, {E}], got {k}")
+    if x.is_cuda and x.dtype == torch.bfloat16 and not _moe_tensor_ok(x):
+        x = x.contiguous()
+    # the dtypes by role: moe_supported takes fp32 and int32 tensors too (weights, ids), the kernel reads bf16
+    if not (x.dtype == w_router.dtype == torch.bfloat16 and moe_supported(T, H, 128, E, k, x) and w_router.is_cuda
+            and w_router.is_contiguous() and w_router.data_ptr() % 16 == 0):
+        return ref.moe_route_ref(x, w_router, k)
+    ids = torch.empty((T, k), device=x.device, dtype=torch.int32)
+    weights = torch.empty((T, k), device=x.device, dtype=torch.float32)
+    check(lib().rca_moe_route(x.data_ptr(), x.stride(0), w_router.data_ptr(), ids.data_ptr(), weights.data_ptr(), T, H, E,
+                              k, stream_ptr(x.device)), "moe_route")
+    return ids, weights
+
+
+def _moe_kernel(x, ids, weights, w_gate_up, w_down, out):
+    """The four launches on operands ``moe_supported`` accepts, whatever T is."""
+    (T, H), (E, _, I), k = x.shape, w_down.shape, ids.shape[1]
+    L = lib()
+    nbytes = int(L.rca_moe_ffn_workspace(T, H, I, E, k))
+    ws = _workspace(x.device, "moe_ffn", (nbytes + 3) // 4)
+    check(L.rca_moe_ffn(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), ids.data_ptr(), weights.data_ptr(),
+                        w_gate_up.data_ptr(), w_down.data_ptr(), ws.data_ptr(), ws.numel() * 4, T, H, I, E, k,
+                        stream_ptr(x.device)), "moe_ffn")
+    return out
+
+
+def moe_ffn(x, ids, weights, w_gate_up, w_down, out=None):
+    """The mixture-of-experts SwiGLU FFN: ``y[t] = sum_j weights[t, j] * down_e(silu(gate_e x[t]) *
+    up_e x[t])`` with ``e = ids[t, j]``, for ``x [T, H]``, ``ids`` / ``weights [T, k]`` (``moe_route``),
+    ``w_gate_up [E, 2I, H]`` (gate rows, then up rows) and ``w_down [E, H, I]``.
+    ``reference.moe_ffn_ref`` has the arithmetic: fp32 sums, the activation rounded to bf16 once, the
+    output rounded once. No autograd: inference only (the reference is differentiable).
+
+    bf16 CUDA operands within ``moe_supported``: up to ``M_MOE`` rows (and any number under stream
+    capture) run the four gfx950 kernels of ``ops/csrc/moe.hip``: the pairs are grouped by expert on
+    the device, so there is no host read and the call can be captured in a graph; an output row depends
+    on its own input row, ids and weights only, bitwise, whatever the batch is. More rows (prefill) run
+    ``reference.moe_ffn_grouped``. An ``x`` with a non-unit inner stride or a misaligned base is made
+    contiguous first. CPU tensors, other dtypes and shapes outside the contract run the reference.
+    ``out``: a ``[T, H]`` tensor or view of ``x.dtype`` to write."""
+    if x.dim() != 2 or ids.dim() != 2 or w_gate_up.dim() != 3 or w_down.dim() != 3:
+        raise ValueError("moe_ffn: x [T, H], ids [T, k], w_gate_up [E, 2I, H] and w_down [E, H, I] are expected")
+    (T, H), (E, _, I), k = x.shape, w_down.shape, ids.shape[1]
+    if (ids.shape[0] != T or tuple(weights.shape) != (T, k) or tuple(w_gate_up.shape) != (E, 2 * I, H)
+            or w_down.shape[1] != H):
+        raise ValueError(f"moe_ffn: x {tuple(x.shape)}, ids {tuple(ids.shape)}, weights {tuple(weights.shape)}, "
+                         f"w_gate_up {tuple(w_gate_up.shape)} and w_down {tuple(w_down.shape)} do not agree")
+    if out is not None and (tuple(out.shape) != (T, H) or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError(f"moe_ffn: out must be a {x.dtype} [{T}, {H}] tensor on {x.device}")
+    if x.is_cuda and x.dtype == torch.bfloat16 and not _moe_tensor_ok(x):
+        x = x.contiguous()
+    bf16 = x.dtype == w_gate_up.dtype == w_down.dtype == torch.bfloat16  # the dtypes by role, as in moe_route
+    if not (bf16 and ids.dtype == torch.int32 and weights.dtype == torch.float32
+            and moe_supported(T, H, I, E, k, x, ids, weights, w_gate_up, w_down)):
+        y = ref.moe_ffn_ref(x, ids, weights, w_gate_up, w_down)
+    elif T <= M_MOE or torch.cuda.is_current_stream_capturing():
+        direct = out is not None and _moe_tensor_ok(out)
+        y = _moe_kernel(x, ids, weights, w_gate_up, w_down,
+                        out if direct else torch.empty((T, H), device=x.device, dtype=x.dtype))
+        if direct:
+            return out
+    else:
+        y = ref.moe_ffn_grouped(x, ids, weights, w_gate_up, w_down)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y

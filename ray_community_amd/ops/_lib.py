@@ -107,6 +107,10 @@ _SIGS = {
     "rca_lora_splits": (c_int, [c_int, c_int]),
     "rca_lora_add": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_int, c_void_p, c_ll] + [c_int] * 5
                      + [c_void_p]),
+    "rca_moe_down_splits": (c_int, [c_int, c_int]),
+    "rca_moe_ffn_workspace": (c_ll, [c_int] * 5),
+    "rca_moe_route": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "rca_moe_ffn": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_ll] + [c_int] * 5 + [c_void_p]),
 }
 
 

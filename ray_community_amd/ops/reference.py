@@ -544,3 +544,72 @@ def token_logprobs_ref(logits, tokens, top_n=0):
         top_ids[:, :n] = order
         top_lp[:, :n] = lp_all.gather(1, order).float()
     return lp.to(logits.device), top_ids.to(logits.device), top_lp.to(logits.device)
+
+
+def _moe_acc(x):
+    return torch.float64 if x.dtype == torch.float64 else torch.float32
+
+
+def moe_route_ref(x, w_router, k):
+    """Top-``k`` routing of ``x [T, H]`` over the ``E`` rows of ``w_router [E, H]``: ``(ids int32
+    [T, k], weights fp32 [T, k])``. The logits are ``x . w_router^T`` accumulated in fp32 (fp64 for
+    fp64 operands); ``ids`` are the ``k`` largest in descending order, equal logits by ascending expert
+    index (a stable descending sort); ``weights`` is the softmax over those ``k`` logits, which is
+    Mixtral's softmax over all experts followed by renormalisation. The contract of ``ops.moe_route``."""
+    acc = _moe_acc(x)
+    logits = x.to(acc) @ w_router.to(acc).t()
+    order = torch.sort(logits, dim=1, descending=True, stable=True).indices[:, :k]
+    weights = torch.softmax(logits.gather(1, order), dim=1)
+    return order.to(torch.int32), weights.float()
+
+
+def moe_ffn_ref(x, ids, weights, w_gate_up, w_down):
+    """Mixture-of-experts SwiGLU FFN ``[T, H]`` in ``x.dtype``. ``w_gate_up [E, 2I, H]`` (gate rows, then
+    up rows), ``w_down [E, H, I]``; for pair ``p = t k + j`` with expert ``e = ids[t, j]``
+
+        g, u   = fp32 sums of w_gate_up[e] . x[t]
+        act[p] = x.dtype(silu(g) * u)                       one rounding; g and u are not rounded
+        d[p]   = fp32 sums of w_down[e] . act[p]
+        y[t]   = x.dtype(sum_j weights[t, j] * d[t k + j])  ascending j, fp32
+
+    (fp64 throughout for fp64 operands). A pair whose id is outside ``[0, E)`` adds nothing.
+    Differentiable in ``x``, ``weights`` and the expert weights. The contract of ``ops.moe_ffn`` and its
+    path for CPU tensors, other dtypes and shapes outside the kernel's contract."""
+    acc = _moe_acc(x)
+    (T, k), E, I = ids.shape, w_gate_up.shape[0], w_down.shape[2]
+    flat = ids.reshape(-1).long()
+    d = torch.zeros(T * k, x.shape[1], dtype=acc, device=x.device)
+    for e in range(E):
+        pairs = (flat == e).nonzero().reshape(-1)
+        if pairs.numel() == 0:
+            continue
+        gu = x[pairs // k].to(acc) @ w_gate_up[e].to(acc).t()
+        act = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]).to(x.dtype)
+        d = d.index_copy(0, pairs, act.to(acc) @ w_down[e].to(acc).t())
+    d = d.view(T, k, -1)
+    y = weights[:, 0, None].to(acc) * d[:, 0]
+    for j in range(1, k):
+        y = y + weights[:, j, None].to(acc) * d[:, j]
+    return y.to(x.dtype)
+
+
+def moe_ffn_grouped(x, ids, weights, w_gate_up, w_down):
+    """``moe_ffn_ref`` for many rows: the pairs sorted by expert (one host read of the counts), then one
+    ``F.linear`` pair per expert over that expert's rows in ``x.dtype``, so the expert weights are never
+    upcast; ``g``, ``u`` and ``d`` are rounded to ``x.dtype`` by those products, as in the dense MLP. The
+    weighted sum over ``j`` is fp32. Inference only."""
+    F = torch.nn.functional
+    (T, k), E, I = ids.shape, w_gate_up.shape[0], w_down.shape[2]
+    flat = ids.reshape(-1).long()
+    flat = torch.where((flat >= 0) & (flat < E), flat, torch.full_like(flat, E))  # bad ids sort last
+    order = torch.argsort(flat, stable=True)
+    counts = torch.bincount(flat, minlength=E + 1)[:E].tolist()
+    xs = x[order // k]
+    d = torch.zeros(T * k, x.shape[1], dtype=x.dtype, device=x.device)
+    at = 0
+    for e, n in enumerate(counts):
+        if n:
+            gu = F.linear(xs[at: at + n], w_gate_up[e])
+            d[order[at: at + n]] = F.linear(F.silu(gu[:, :I].float()).mul_(gu[:, I:].float()).to(x.dtype), w_down[e])
+            at += n
+    return (d.view(T, k, -1).float() * weights[:, :, None].float()).sum(dim=1).to(x.dtype)
