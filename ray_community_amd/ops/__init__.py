@@ -856,9 +856,14 @@ def batch_norm_act(x, weight, bias, running_mean=None, running_var=None, trainin
     PyTorch composition with identical semantics (batch statistics, biased variance for
     normalisation, unbiased variance in the running estimate)."""
     use_kernel = training and bn_supported(x) and (residual is None or residual.shape == x.shape)
-    if use_kernel and weight is not None and weight.dtype != torch.float32:
+    # the kernels read gamma, beta and the running statistics as contiguous float rows of C
+    if use_kernel and any(t is not None and t.dtype != torch.float32 for t in (weight, bias, running_mean, running_var)):
+        use_kernel = False
+    if use_kernel and any(t is not None and not t.is_contiguous() for t in (weight, bias, running_mean, running_var)):
         use_kernel = False
     if not use_kernel:
+        if weight is not None and bias is not None and bias.dtype != weight.dtype:
+            bias = bias.to(weight.dtype)  # torch's batch_norm wants one parameter dtype
         y = torch.nn.functional.batch_norm(x, running_mean, running_var, weight, bias, training, momentum, eps)
         if residual is not None:
             y = y + residual
