@@ -148,7 +148,8 @@ class MoEMLP(nn.Module):
     ``num_experts`` SwiGLU MLPs per token and the block's output is their softmax-weighted sum.
     ``router.weight [E, H]``, ``w_gate_up [E, 2I, H]`` (gate rows, then up rows: the dense fused order)
     and ``w_down [E, H, I]``. Inference runs ``ops.moe_route`` and ``ops.moe_ffn``; under autograd the
-    differentiable torch reference runs (no load-balancing loss)."""
+    differentiable torch reference runs (no load-balancing loss). After ``quantize_experts_`` the expert
+    weights are MXFP4 buffers and inference runs ``ops.moe_ffn_w4``."""
 
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -161,7 +162,28 @@ class MoEMLP(nn.Module):
         self.w_gate_up = nn.Parameter(torch.empty(E, 2 * I, H))
         self.w_down = nn.Parameter(torch.empty(E, H, I))
 
+    @torch.no_grad()
+    def quantize_experts_(self):
+        """Replace the parameters ``w_gate_up`` and ``w_down`` by their MXFP4 form, the uint8 buffers ``q_gate_up
+        [E, 2I, H/2]``, ``s_gate_up [E, 2I, H/32]``, ``q_down [E, H, I/2]`` and ``s_down [E, H, I/32]``
+        (``ops.reference.quantize_experts_mxfp4_ref``), and free the originals; ``forward`` then runs
+        ``ops.moe_ffn_w4``. The router stays as it is. Idempotent; inference only afterwards."""
+        if self.w_gate_up is not None:
+            for name in ("gate_up", "down"):
+                q, s = ops.reference.quantize_experts_mxfp4_ref(getattr(self, "w_" + name).detach())
+                delattr(self, "w_" + name)
+                setattr(self, "w_" + name, None)  # a plain attribute: no parameter of that name is left
+                self.register_buffer("q_" + name, q.contiguous())
+                self.register_buffer("s_" + name, s.contiguous())
+        return self
+
     def forward(self, x):
+        if self.w_gate_up is None:
+            if torch.is_grad_enabled():
+                raise RuntimeError("MoEMLP with quantised experts is inference-only (mxfp4 weights have no gradient): "
+                                   "call it under torch.no_grad() or torch.inference_mode()")
+            ids, weights = ops.moe_route(x, self.router.weight, self.top_k)
+            return ops.moe_ffn_w4(x, ids, weights, self.q_gate_up, self.s_gate_up, self.q_down, self.s_down)
         if torch.is_grad_enabled() and (x.requires_grad or self.w_down.requires_grad):
             ids, weights = ops.reference.moe_route_ref(x, self.router.weight, self.top_k)
             return ops.reference.moe_ffn_ref(x, ids, weights, self.w_gate_up, self.w_down)
@@ -216,6 +238,24 @@ class Llama(nn.Module):
             raise NotImplementedError("quantised expert weights are not implemented for MoE models")
         self.module_epoch += 1
         return quantize_weights_(self, dtype)
+
+    def quantize_experts_(self, dtype="mxfp4"):
+        """Quantise the expert weights of a MoE model in place for inference: ``"mxfp4"`` turns every block's
+        ``w_gate_up`` / ``w_down`` into OCP MXFP4 buffers (``MoEMLP.quantize_experts_``: 17/32 of a byte a
+        weight), and ``prefill`` / ``extend`` / ``decode_step`` / ``generate`` then run ``ops.moe_ffn_w4``.
+        Attention, the router, the embedding and the head stay as they are. ``None`` / ``"auto"`` leave the
+        model alone; any other dtype, or a dense model, raises ``ValueError``. Idempotent."""
+        if dtype not in (None, "auto", "mxfp4"):
+            raise ValueError(f"expert dtype must be one of (None, 'auto', 'mxfp4'), got {dtype!r}")
+        if dtype != "mxfp4":
+            return self
+        if not self.cfg.num_experts:
+            raise ValueError("quantize_experts_ needs a MoE model (num_experts > 0)")
+        self.module_epoch += 1
+        for blk in self.layers:
+            blk.mlp.quantize_experts_()
+        self.expert_dtype = dtype
+        return self
 
     def enable_lora_(self, max_adapters: int, max_rank: int):
         """Make room for ``max_adapters`` LoRA adapters of up to ``max_rank`` per projection
@@ -587,9 +627,11 @@ _SEQ_IDS = itertools.count()
 from .decoding import _seeded_generator, sample_tokens, use_fused_sampling  # noqa: E402,F401
 
 
-def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, weight_dtype=None, **overrides) -> Llama:
+def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, weight_dtype=None, expert_dtype=None,
+                **overrides) -> Llama:
     """``weight_dtype``: ``None`` / ``"auto"`` keep the linears in ``dtype``; ``"fp8"`` / ``"mxfp4"`` quantise
-    them (``Llama.quantize_weights_``) after the cast."""
+    them (``Llama.quantize_weights_``) after the cast. ``expert_dtype``: ``"mxfp4"`` quantises the experts of a
+    MoE model (``Llama.quantize_experts_``) after the cast; ``None`` / ``"auto"`` keep them in ``dtype``."""
     cfg = PRESETS[name_or_cfg] if isinstance(name_or_cfg, str) else name_or_cfg
     if overrides:
         cfg = LlamaConfig(**{**cfg.__dict__, **overrides})
@@ -598,4 +640,4 @@ def build_llama(name_or_cfg="llama3-8b", device=None, dtype=torch.bfloat16, weig
             m = Llama(cfg)
     else:
         m = Llama(cfg)
-    return m.to(dtype=dtype).quantize_weights_(weight_dtype)
+    return m.to(dtype=dtype).quantize_weights_(weight_dtype).quantize_experts_(expert_dtype)

@@ -60,6 +60,9 @@ __all__ = [
     "moe_route",
     "moe_ffn",
     "moe_supported",
+    "moe_ffn_w4",
+    "moe_w4_supported",
+    "M_MOE_W4",
     "kernels_available",
 ]
 
@@ -2037,6 +2040,88 @@ def moe_ffn(x, ids, weights, w_gate_up, w_down, out=None):
             return out
     else:
         y = ref.moe_ffn_grouped(x, ids, weights, w_gate_up, w_down)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
+
+
+# Rows up to which ``moe_ffn_w4`` runs the grouped W4A16 expert kernels (ops/csrc/moe_w4.hip); above it every
+# expert in use is dequantised into a bf16 workspace and takes two ``F.linear``s over its rows. The largest
+# measured T at which the kernels beat that arm at the mixtral-8x7b layer shape in the same process
+# (``scripts/moe_bench.py --format mxfp4``, T in 1, 8, 32, 64, 128): they win at every measured T, by 4.8x at
+# T = 128, so the crossover lies above what was measured: profiles/moe_w4.md has the table.
+M_MOE_W4 = 128
+
+
+def moe_w4_supported(T: int, H: int, I: int, E: int, k: int, *tensors) -> bool:
+    """What the W4 MoE kernels take: ``H % 256 == 0``, ``I % 256 == 0``, ``T >= 1``, ``2 <= E <= 64``, ``1 <= k <=
+    min(E, 8)``; CUDA tensors with 16-byte aligned bases: bf16 2-D ``x`` / ``y`` with unit inner stride and a row
+    stride that is a multiple of 8, contiguous uint8 3-D nibble pairs and E8M0 scales, contiguous int32 ``ids``
+    and fp32 ``weights``. A tensor is judged by its own dtype, as in ``moe_supported``."""
+    def ok(t):
+        if torch.is_tensor(t) and t.dtype == torch.uint8:
+            return t.is_cuda and t.dim() == 3 and t.is_contiguous() and t.data_ptr() % 16 == 0
+        return _moe_tensor_ok(t) and t.dim() == 2
+    return (T >= 1 and H > 0 and I > 0 and H % 256 == 0 and I % 256 == 0 and 2 <= E <= MOE_MAX_EXPERTS
+            and 1 <= k <= min(E, MOE_MAX_TOP_K) and all(ok(t) for t in tensors))
+
+
+def _moe_w4_kernel(x, ids, weights, q_gate_up, s_gate_up, q_down, s_down, out):
+    """The four launches on operands ``moe_w4_supported`` accepts, whatever T is."""
+    (T, H), E, I, k = x.shape, q_down.shape[0], q_down.shape[2] * 2, ids.shape[1]
+    L = lib()
+    nbytes = int(L.rca_moe_ffn_w4_workspace(T, H, I, E, k))
+    ws = _workspace(x.device, "moe_ffn", (nbytes + 3) // 4)  # the bf16 kernels' layout: one workspace for both
+    check(L.rca_moe_ffn_w4(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), ids.data_ptr(), weights.data_ptr(),
+                           q_gate_up.data_ptr(), s_gate_up.data_ptr(), q_down.data_ptr(), s_down.data_ptr(),
+                           ws.data_ptr(), ws.numel() * 4, T, H, I, E, k, stream_ptr(x.device)), "moe_ffn_w4")
+    return out
+
+
+def moe_ffn_w4(x, ids, weights, q_gate_up, s_gate_up, q_down, s_down, out=None):
+    """``moe_ffn`` over MXFP4 expert weights (W4A16): ``q_gate_up [E, 2I, H/2]`` / ``q_down [E, H, I/2]`` uint8
+    e2m1 nibble pairs (the low nibble the even ``k``) and ``s_gate_up [E, 2I, H/32]`` / ``s_down [E, H, I/32]``
+    uint8 E8M0 block scales, any value in ``[2, 252]`` (``reference.quantize_experts_mxfp4_ref``: each expert matrix
+    quantised row by row as ``linear_w4``'s weight is). ``reference.moe_ffn_w4_ref`` has the arithmetic: the
+    exactly dequantised weights, fp32 sums, the activation rounded to bf16 once, the output rounded once. No
+    autograd: inference only.
+
+    bf16 CUDA ``x`` within ``moe_w4_supported``: up to ``M_MOE_W4`` rows (and any number under stream capture)
+    run the four gfx950 kernels of ``ops/csrc/moe_w4.hip``: the nibbles are streamed and converted to bf16 in
+    registers with their block scale applied; no host read, so the call can be captured in a graph; an output
+    row depends on its own input row, ids and weights only, bitwise, whatever the batch is. More rows (prefill)
+    dequantise each expert in use into one per-device bf16 workspace (``dequant_w4``) for the two ``F.linear``s
+    of ``reference.moe_ffn_grouped``; the 4-bit bytes stay the only resident copy. An ``x`` with a non-unit
+    inner stride or a misaligned base is made contiguous first. CPU tensors, other dtypes and shapes outside
+    the contract run the reference. ``out``: a ``[T, H]`` tensor or view of ``x.dtype`` to write."""
+    quads = (q_gate_up, s_gate_up, q_down, s_down)
+    if x.dim() != 2 or ids.dim() != 2 or any(t.dim() != 3 or t.dtype != torch.uint8 for t in quads):
+        raise ValueError("moe_ffn_w4: x [T, H], ids [T, k] and uint8 q_gate_up [E, 2I, H/2], s_gate_up [E, 2I, H/32], "
+                         "q_down [E, H, I/2], s_down [E, H, I/32] are expected")
+    (T, H), E, I, k = x.shape, q_down.shape[0], q_down.shape[2] * 2, ids.shape[1]
+    if (ids.shape[0] != T or tuple(weights.shape) != (T, k) or H % 32 or I % 32
+            or tuple(q_gate_up.shape) != (E, 2 * I, H // 2) or tuple(s_gate_up.shape) != (E, 2 * I, H // 32)
+            or tuple(q_down.shape) != (E, H, I // 2) or tuple(s_down.shape) != (E, H, I // 32)):
+        raise ValueError(f"moe_ffn_w4: x {tuple(x.shape)}, ids {tuple(ids.shape)}, weights {tuple(weights.shape)}, "
+                         f"q_gate_up {tuple(q_gate_up.shape)}, s_gate_up {tuple(s_gate_up.shape)}, q_down "
+                         f"{tuple(q_down.shape)} and s_down {tuple(s_down.shape)} do not agree")
+    if out is not None and (tuple(out.shape) != (T, H) or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError(f"moe_ffn_w4: out must be a {x.dtype} [{T}, {H}] tensor on {x.device}")
+    if x.is_cuda and x.dtype == torch.bfloat16 and not _moe_tensor_ok(x):
+        x = x.contiguous()
+    if not (x.dtype == torch.bfloat16 and ids.dtype == torch.int32 and weights.dtype == torch.float32
+            and moe_w4_supported(T, H, I, E, k, x, ids, weights, *quads)):
+        y = ref.moe_ffn_w4_ref(x, ids, weights, *quads)
+    elif T <= M_MOE_W4 or torch.cuda.is_current_stream_capturing():
+        direct = out is not None and _moe_tensor_ok(out)
+        y = _moe_w4_kernel(x, ids, weights, *quads, out if direct else torch.empty((T, H), device=x.device, dtype=x.dtype))
+        if direct:
+            return out
+    else:
+        ws = _workspace(x.device, "moe_w4_dequant", 3 * H * I, torch.bfloat16)
+        views = (ws[:2 * I * H].view(2 * I, H), ws[2 * I * H:3 * I * H].view(H, I))
+        y = ref.moe_ffn_w4_grouped(x, ids, weights, *quads, dequant=lambda q, s, slot: dequant_w4(q, s, views[slot]))
     if out is not None:
         out.copy_(y)
         return out

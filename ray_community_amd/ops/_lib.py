@@ -111,6 +111,9 @@ _SIGS = {
     "rca_moe_ffn_workspace": (c_ll, [c_int] * 5),
     "rca_moe_route": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "rca_moe_ffn": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_ll] + [c_int] * 5 + [c_void_p]),
+    "rca_moe_w4_down_splits": (c_int, [c_int, c_int]),
+    "rca_moe_ffn_w4_workspace": (c_ll, [c_int] * 5),
+    "rca_moe_ffn_w4": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 7 + [c_ll] + [c_int] * 5 + [c_void_p]),
 }
 
 

@@ -32,6 +32,7 @@
 // M is and wherever the row sits in the batch. Rows of a 16-row MFMA tile beyond M are zeros in LDS and
 // are not stored; a column of the MFMA result depends on its own column operand only.
 #include "common.h"
+#include "w4_cvt.h"  // w4_cvt8, e8m0
 
 namespace {
 
@@ -51,19 +52,6 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-
-// 4 bytes = 8 e2m1 nibbles (k ascending: low nibble first) times `scale` (a power of two) -> 8 bf16, exact
-__device__ __forceinline__ u32x4 w4_cvt8(unsigned w, float scale) {
-  u32x4 r;
-  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
-  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
-  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
-  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
-  return r;
-}
-
-// the float 2^(e - 127) of an E8M0 byte (2 <= e <= 252: normal)
-__device__ __forceinline__ float e8m0(unsigned e) { return __uint_as_float(e << 23); }
 
 template <int MT, bool SPLIT>
 __global__ __launch_bounds__(256) void linear_w4a16_kernel(const bf16_t* __restrict__ x, long long ldx,

@@ -576,16 +576,24 @@ def moe_ffn_ref(x, ids, weights, w_gate_up, w_down):
     Differentiable in ``x``, ``weights`` and the expert weights. The contract of ``ops.moe_ffn`` and its
     path for CPU tensors, other dtypes and shapes outside the kernel's contract."""
     acc = _moe_acc(x)
-    (T, k), E, I = ids.shape, w_gate_up.shape[0], w_down.shape[2]
+    return _moe_ffn(x, ids, weights, w_gate_up.shape[0], w_down.shape[2],
+                    lambda e: (w_gate_up[e].to(acc), w_down[e].to(acc)))
+
+
+def _moe_ffn(x, ids, weights, E, I, expert):
+    """``moe_ffn_ref`` with ``expert(e)`` giving ``(w_gate_up[e], w_down[e])`` in the accumulation dtype."""
+    acc = _moe_acc(x)
+    T, k = ids.shape
     flat = ids.reshape(-1).long()
     d = torch.zeros(T * k, x.shape[1], dtype=acc, device=x.device)
     for e in range(E):
         pairs = (flat == e).nonzero().reshape(-1)
         if pairs.numel() == 0:
             continue
-        gu = x[pairs // k].to(acc) @ w_gate_up[e].to(acc).t()
+        wgu, wd = expert(e)
+        gu = x[pairs // k].to(acc) @ wgu.t()
         act = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]).to(x.dtype)
-        d = d.index_copy(0, pairs, act.to(acc) @ w_down[e].to(acc).t())
+        d = d.index_copy(0, pairs, act.to(acc) @ wd.t())
     d = d.view(T, k, -1)
     y = weights[:, 0, None].to(acc) * d[:, 0]
     for j in range(1, k):
@@ -598,8 +606,14 @@ def moe_ffn_grouped(x, ids, weights, w_gate_up, w_down):
     ``F.linear`` pair per expert over that expert's rows in ``x.dtype``, so the expert weights are never
     upcast; ``g``, ``u`` and ``d`` are rounded to ``x.dtype`` by those products, as in the dense MLP. The
     weighted sum over ``j`` is fp32. Inference only."""
+    return _moe_grouped(x, ids, weights, w_gate_up.shape[0], w_down.shape[2], lambda e: (w_gate_up[e], w_down[e]))
+
+
+def _moe_grouped(x, ids, weights, E, I, expert):
+    """``moe_ffn_grouped`` with ``expert(e)`` giving ``(w_gate_up[e], w_down[e])`` in ``x.dtype``, asked for once
+    per expert in use, in ascending order; what it returned for the previous expert is no longer needed."""
     F = torch.nn.functional
-    (T, k), E, I = ids.shape, w_gate_up.shape[0], w_down.shape[2]
+    T, k = ids.shape
     flat = ids.reshape(-1).long()
     flat = torch.where((flat >= 0) & (flat < E), flat, torch.full_like(flat, E))  # bad ids sort last
     order = torch.argsort(flat, stable=True)
@@ -609,7 +623,42 @@ def moe_ffn_grouped(x, ids, weights, w_gate_up, w_down):
     at = 0
     for e, n in enumerate(counts):
         if n:
-            gu = F.linear(xs[at: at + n], w_gate_up[e])
-            d[order[at: at + n]] = F.linear(F.silu(gu[:, :I].float()).mul_(gu[:, I:].float()).to(x.dtype), w_down[e])
+            wgu, wd = expert(e)
+            gu = F.linear(xs[at: at + n], wgu)
+            d[order[at: at + n]] = F.linear(F.silu(gu[:, :I].float()).mul_(gu[:, I:].float()).to(x.dtype), wd)
             at += n
     return (d.view(T, k, -1).float() * weights[:, :, None].float()).sum(dim=1).to(x.dtype)
+
+
+def quantize_experts_mxfp4_ref(w):
+    """``quantize_weight_mxfp4_ref`` on every row of the expert matrices ``w [E, N, K]``: ``(q [E, N, K/2],
+    s [E, N, K/32])`` uint8. The blocks run along ``k`` inside a row, so this is the ``[E N, K]`` view quantised
+    and reshaped back."""
+    if w.dim() != 3:
+        raise ValueError("quantize_experts_mxfp4_ref: weight must be [E, N, K]")
+    E, N, K = w.shape
+    q, s = quantize_weight_mxfp4_ref(w.reshape(E * N, K))
+    return q.view(E, N, K // 2), s.view(E, N, K // MXFP4_BLOCK)
+
+
+def moe_ffn_w4_ref(x, ids, weights, q_gate_up, s_gate_up, q_down, s_down):
+    """``moe_ffn_ref`` over MXFP4 experts: ``q_gate_up [E, 2I, H/2]`` / ``s_gate_up [E, 2I, H/32]`` and ``q_down
+    [E, H, I/2]`` / ``s_down [E, H, I/32]`` (``quantize_experts_mxfp4_ref``), each expert dequantised exactly,
+    one at a time, into the accumulation dtype. The activation is rounded once and the sums are fp32, as there.
+    The contract of ``ops.moe_ffn_w4`` and its path for CPU tensors, other dtypes and shapes outside the
+    kernel's contract."""
+    acc = _moe_acc(x)
+    return _moe_ffn(x, ids, weights, q_down.shape[0], q_down.shape[2] * 2,
+                    lambda e: (dequantize_mxfp4_ref(q_gate_up[e], s_gate_up[e], acc),
+                               dequantize_mxfp4_ref(q_down[e], s_down[e], acc)))
+
+
+def moe_ffn_w4_grouped(x, ids, weights, q_gate_up, s_gate_up, q_down, s_down, dequant=None):
+    """``moe_ffn_grouped`` over MXFP4 experts: every expert in use is dequantised into ``x.dtype`` right before
+    its two ``F.linear``s, by ``dequant(q, s, slot)`` (``slot`` 0: gate_up, 1: down, so that a caller can reuse
+    one workspace per matrix; default ``dequantize_mxfp4_ref``). The 4-bit bytes stay the only resident copy.
+    Inference only."""
+    if dequant is None:
+        dequant = lambda q, s, slot: dequantize_mxfp4_ref(q, s, x.dtype)  # noqa: E731
+    return _moe_grouped(x, ids, weights, q_down.shape[0], q_down.shape[2] * 2,
+                        lambda e: (dequant(q_gate_up[e], s_gate_up[e], 0), dequant(q_down[e], s_down[e], 1)))

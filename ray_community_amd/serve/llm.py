@@ -22,7 +22,8 @@ class _LlamaDeployment:
     def __init__(self, model="llama3-tiny", state_dict_path=None, device="cpu", dtype="bfloat16", max_slots: int = 8,
                  num_blocks=None, page_size: int = 16, seed: int = 0, default_max_new_tokens: int = 16,
                  prefill_chunk=None, fused_sampling: bool = False, speculative=None, kv_cache_dtype=None,
-                 cache_bytes=None, weight_dtype=None, lora=None, adapters=None, graph_decode: bool = False):
+                 cache_bytes=None, weight_dtype=None, lora=None, adapters=None, graph_decode: bool = False,
+                 expert_dtype=None):
         """``model``: a preset name or a ``LlamaConfig``; ``state_dict_path``: optional
         ``torch.save``d state dict (without one the weights are initialised from ``seed``);
         ``prefill_chunk``: prompt tokens the engine spends per step (chunked prefill: a long prompt
@@ -36,7 +37,9 @@ class _LlamaDeployment:
         ``GenerationEngine``; ``weight_dtype`` (``None`` / ``"auto"`` / ``"fp8"`` / ``"mxfp4"``): ``"fp8"`` and
         ``"mxfp4"`` quantise the linears' weights once the state dict is loaded
         (``Llama.quantize_weights_``: a half and about a quarter of the bf16 weight bytes,
-        activations stay in ``dtype``); ``lora={"max_adapters": n, "max_rank": r}``
+        activations stay in ``dtype``); ``expert_dtype`` (``None`` / ``"auto"`` / ``"mxfp4"``): ``"mxfp4"`` quantises
+        the expert weights of a MoE model (``Llama.quantize_experts_``; attention, router and head stay in
+        ``dtype``); ``lora={"max_adapters": n, "max_rank": r}``
         makes room for LoRA adapters (``Llama.enable_lora_``, after the quantisation) that requests
         select by name, and ``adapters={"name": path}`` preloads ``LoraAdapter.save``d files;
         ``graph_decode``: the engine replays its decode step as a captured HIP graph
@@ -50,6 +53,7 @@ class _LlamaDeployment:
         if state_dict_path is not None:
             self.model.load_state_dict(torch.load(state_dict_path, map_location=device))
         self.model.quantize_weights_(weight_dtype)
+        self.model.quantize_experts_(expert_dtype)
         self.lora = None
         if lora is not None:
             self.lora = {"max_adapters": int(lora["max_adapters"]), "max_rank": int(lora["max_rank"])}
@@ -60,6 +64,7 @@ class _LlamaDeployment:
             self.model.load_adapter(name, LoraAdapter.load(path))
         self.model.eval()
         self.weight_dtype = weight_dtype if weight_dtype in ("fp8", "mxfp4") else None
+        self.expert_dtype = expert_dtype if expert_dtype == "mxfp4" else None
         self.weight_bytes = weight_bytes(self.model)
         self.engine = GenerationEngine(self.model, max_slots=max_slots, num_blocks=num_blocks, page_size=page_size,
                                        prefill_chunk=prefill_chunk, fused_sampling=fused_sampling,
@@ -169,6 +174,7 @@ class _LlamaDeployment:
         ``speculative`` adds ``"speculative": {"num_draft", **engine.spec_stats}``, one with an fp8
         cache adds ``"kv_cache_dtype": "fp8"``, ``"num_blocks"`` and ``"cache_bytes"``, one with fp8
         or mxfp4 weights adds ``"weight_dtype": "fp8"`` / ``"mxfp4"`` and ``"weight_bytes"`` (the model's parameters and buffers),
+        one with mxfp4 experts adds ``"expert_dtype": "mxfp4"`` and ``"weight_bytes"``,
         one with ``lora`` adds ``"lora": {"max_adapters", "max_rank", "loaded": [...], "bank_bytes"}``,
         one with ``graph_decode`` adds ``"graph_decode": {"graphs", "replays", "eager_warm", "eager_fallback"}``."""
         streams = [{"request_id": rid, "max_new_tokens": e[1], "produced": e[2]}
@@ -186,6 +192,8 @@ class _LlamaDeployment:
             st.update(kv_cache_dtype="fp8", num_blocks=cache.num_blocks, cache_bytes=cache.nbytes)
         if self.weight_dtype is not None:
             st.update(weight_dtype=self.weight_dtype, weight_bytes=self.weight_bytes)
+        if self.expert_dtype is not None:
+            st.update(expert_dtype=self.expert_dtype, weight_bytes=self.weight_bytes)
         if self.lora is not None:
             from ..models.lora import bank_bytes
 

@@ -10,12 +10,18 @@ power-of-two T at which the kernels win.
 End to end: ``Llama.generate`` tokens/s, eager against ``graph_decode=True``, on ``mixtral-tiny`` and on a
 ``mixtral-8x7b`` stack cut to ``--layers`` layers, at batch 1 and 8.
 
-    python scripts/moe_bench.py [--rounds 7] [--layers 2] [--rows 1,8,...] [--no-e2e] [--json out.json]
+    python scripts/moe_bench.py [--rounds 7] [--layers 2] [--rows 1,8,...] [--no-e2e] [--json out.json] [--format mxfp4]
 
 ``--rows`` times other batch sizes, such as the thousands of rows of a captured prefill (one align workgroup).
+``--format mxfp4``: the experts are MXFP4 (random nibbles and block scales). Three arms alternate: the W4 kernels
+of ``ops/csrc/moe_w4.hip`` (``ops._moe_w4_kernel``), ``ops.moe_ffn_w4``'s dequantise-and-group arm and the bf16
+kernels on the dequantised weights; ``TB/s`` is over the bytes the arm's weights occupy (17/32 of a byte a weight
+for the first two). ``M_MOE_W4`` is the largest measured T at which the W4 kernels beat the dequantise-and-group
+arm. The ``generate`` rows run with ``expert_dtype="mxfp4"``.
 """
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -42,21 +48,48 @@ def _time(fn, iters):
     return start.elapsed_time(end) * 1e3 / iters  # us
 
 
-def op_bench(rounds, iters, rows_list=TS):
+def _random_mxfp4(E, N, K, g):
+    """Random nibbles and E8M0 bytes 8 wide around 2^-1 / (3 sqrt(K)): weights of the size 1 / sqrt(K), as the bf16 arm draws."""
+    mid = 127 - 1 - round(math.log2(3 * K ** 0.5))
+    q = torch.randint(0, 256, (E, N, K // 2), device="cuda", dtype=torch.uint8, generator=g)
+    return q, torch.randint(mid - 4, mid + 4, (E, N, K // 32), device="cuda", dtype=torch.uint8, generator=g)
+
+
+def op_bench(rounds, iters, rows_list=TS, fmt="bf16"):
+    """bf16: the bf16 kernels ("hip") against the grouped torch arm. mxfp4: the W4 kernels ("hip") against the op's
+    dequantise-and-group arm ("grouped") and the bf16 kernels on the dequantised weights ("bf16_hip")."""
     cfg = LLAMA_PRESETS["mixtral-8x7b"]
     H, I, E, k = cfg.hidden_size, cfg.intermediate_size, cfg.num_experts, cfg.experts_per_token
     g = torch.Generator(device="cuda").manual_seed(0)
     router = (torch.randn(E, H, device="cuda", generator=g) / H ** 0.5).bfloat16()
-    wgu = (torch.randn(E, 2 * I, H, device="cuda", generator=g) / H ** 0.5).bfloat16()
-    wd = (torch.randn(E, H, I, device="cuda", generator=g) / I ** 0.5).bfloat16()
+    if fmt == "mxfp4":
+        quads = [t for name, N, K in (("gate_up", 2 * I, H), ("down", H, I)) for t in _random_mxfp4(E, N, K, g)]
+        wgu, wd = (torch.stack([ops.dequant_w4(q[e], s[e]) for e in range(E)]) for q, s in (quads[:2], quads[2:]))
+    else:
+        wgu = (torch.randn(E, 2 * I, H, device="cuda", generator=g) / H ** 0.5).bfloat16()
+        wd = (torch.randn(E, H, I, device="cuda", generator=g) / I ** 0.5).bfloat16()
+    own = 3 * H * I * (17 / 32 if fmt == "mxfp4" else 2)  # an expert's resident bytes; the bf16 kernels stream bf16
+    nbytes = {"hip": own, "grouped": own}
     rows = []
     for T in rows_list:
         x = torch.randn(T, H, device="cuda", dtype=torch.bfloat16, generator=g)
         ids, weights = ops.moe_route(x, router, k)
         assert ops.moe_supported(T, H, I, E, k, x, ids, weights, wgu, wd)
         out = torch.empty_like(x)
-        arms = {"hip": lambda: ops._moe_kernel(x, ids, weights, wgu, wd, out),
-                "grouped": lambda: ref.moe_ffn_grouped(x, ids, weights, wgu, wd)}
+        if fmt == "mxfp4":
+            assert ops.moe_w4_supported(T, H, I, E, k, x, ids, weights, *quads)
+
+            def grouped():  # the op's own arm above M_MOE_W4 rows
+                keep, ops.M_MOE_W4 = ops.M_MOE_W4, 0
+                try:
+                    return ops.moe_ffn_w4(x, ids, weights, *quads)
+                finally:
+                    ops.M_MOE_W4 = keep
+            arms = {"hip": lambda: ops._moe_w4_kernel(x, ids, weights, *quads, out), "grouped": grouped,
+                    "bf16_hip": lambda: ops._moe_kernel(x, ids, weights, wgu, wd, out)}
+        else:
+            arms = {"hip": lambda: ops._moe_kernel(x, ids, weights, wgu, wd, out),
+                    "grouped": lambda: ref.moe_ffn_grouped(x, ids, weights, wgu, wd)}
         diff = (arms["hip"]().float() - arms["grouped"]().float()).abs().max().item()
         times = {name: [] for name in arms}
         for fn in arms.values():
@@ -65,19 +98,20 @@ def op_bench(rounds, iters, rows_list=TS):
             for name, fn in arms.items():
                 times[name].append(_time(fn, iters))
         used = int(torch.unique(ids).numel())
-        row = {"T": T, "experts_used": used, "weight_gb": used * 3 * H * I * 2 / 1e9, "max_diff": diff}
+        row = {"T": T, "format": fmt, "experts_used": used, "weight_gb": used * nbytes["hip"] / 1e9, "max_diff": diff}
         for name, ts in times.items():
             med = statistics.median(ts)
-            row[name] = {"us": med, "min_us": min(ts), "max_us": max(ts), "tb_s": used * 3 * H * I * 2 / med / 1e6}
+            row[name] = {"us": med, "min_us": min(ts), "max_us": max(ts),
+                         "tb_s": used * nbytes.get(name, 3 * H * I * 2) / med / 1e6}
         rows.append(row)
         print(json.dumps(row), flush=True)
     return rows
 
 
-def e2e_bench(name, layers, rounds, new_tokens=64):
+def e2e_bench(name, layers, rounds, new_tokens=64, fmt="bf16"):
     torch.manual_seed(0)
     over = {} if layers is None else {"num_layers": layers}
-    model = build_llama(name, device="cuda", max_seq_len=512, **over).eval()
+    model = build_llama(name, device="cuda", max_seq_len=512, expert_dtype="mxfp4" if fmt == "mxfp4" else None, **over).eval()
     rows = []
     for batch in (1, 8):
         g = torch.Generator().manual_seed(batch)
@@ -109,12 +143,15 @@ def main():
     ap.add_argument("--rows", type=lambda s: [int(t) for t in s.split(",")], default=TS)
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--json")
+    ap.add_argument("--format", choices=("bf16", "mxfp4"), default="bf16", help="the expert weights' format")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("moe_bench.py needs a GPU")
-    result = {"device": torch.cuda.get_device_name(0), "op": op_bench(args.rounds, args.iters, args.rows)}
+    fmt = args.format
+    result = {"device": torch.cuda.get_device_name(0), "format": fmt, "op": op_bench(args.rounds, args.iters, args.rows, fmt)}
     if not args.no_e2e:
-        result["e2e"] = e2e_bench("mixtral-tiny", None, args.rounds) + e2e_bench("mixtral-8x7b", args.layers, args.rounds)
+        result["e2e"] = (e2e_bench("mixtral-tiny", None, args.rounds, fmt=fmt)
+                         + e2e_bench("mixtral-8x7b", args.layers, args.rounds, fmt=fmt))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(result, f, indent=1)
