@@ -1093,9 +1093,10 @@ def flash_attention(q, k, v, causal: bool = True, scale=None):
 
 # ------------------------------------------------------------------- paged KV cache / decode
 def paged_decode_supported(page_size: int, head_dim: int, n_q_heads: int, n_kv_heads: int) -> bool:
-    """Shapes the gfx950 cache-append and paged decode kernels cover (others use the reference)."""
+    """Shapes the gfx950 cache-append and paged decode kernels cover (others use the reference):
+    pages of a multiple of 16 tokens, head_dim 64 or 128, 1, 2, 4, 8 or 16 query heads per kv head."""
     return (page_size > 0 and page_size % 16 == 0 and head_dim in (64, 128) and n_kv_heads > 0
-            and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8))
+            and n_q_heads % n_kv_heads == 0 and n_q_heads // n_kv_heads in (1, 2, 4, 8, 16))
 
 
 def paged_kv_fp8_supported(page_size: int, head_dim: int, n_q_heads: int, n_kv_heads: int) -> bool:
@@ -1270,7 +1271,7 @@ def _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D, *more) -> bool:
 
 
 def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens, Hq: int, Hk: int, D: int,
-                           scale=None, num_splits=None, k_scale=None, v_scale=None):
+                           scale=None, num_splits=None, k_scale=None, v_scale=None, kernel="auto"):
     """Single-token attention of ``B`` sequences over their paged KV caches. Returns ``[B, Hq*D]``.
 
     ``q_or_qkv`` is ``[B, Hq*D]`` or the fused ``[B, (Hq+2Hk)*D]`` row, whose q heads are read in
@@ -1282,16 +1283,36 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
 
     With ``k_scale`` / ``v_scale`` (fp32 ``[num_blocks, page_size, Hk]``) the caches are
     ``float8_e4m3fn`` as ``kv_cache_append_`` wrote them; the result is the attention over the
-    dequantised cache (byte times scale, exact in bf16)."""
+    dequantised cache (byte times scale, exact in bf16).
+
+    ``kernel`` picks the gfx950 kernel. ``"auto"``: 16 query heads per kv head run the MFMA kernel
+    (``ops/csrc/attention_decode_mfma.hip``: the group is the 16 columns of a matrix instruction,
+    probabilities rounded to bf16), up to 8 the VALU kernel (fp32 probabilities), and 8 the MFMA
+    kernel too while ``RCA_ATTN_DECODE=mfma`` is in the environment (read at every call: the
+    end-to-end A/B switch). ``"valu"`` / ``"mfma"`` name one and raise ``ValueError`` for a call it
+    does not take (``"valu"``: 16 heads per kv head; ``"mfma"``: not 8 or 16, or a call that runs on
+    the reference path); neither ever falls back."""
     q = q_or_qkv
     B = _check_paged_attention("B", q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, k_scale, v_scale)
     if num_splits is not None and int(num_splits) < 1:
         raise ValueError("num_splits must be >= 1")
+    if kernel not in ("auto", "valu", "mfma"):
+        raise ValueError(f"kernel must be 'auto', 'valu' or 'mfma', got {kernel!r}")
     scale = float(D ** -0.5 if scale is None else scale)
     num_blocks, page = k_cache.shape[0], k_cache.shape[1]
+    G = Hq // Hk
+    if kernel == "valu" and G == 16:
+        raise ValueError("kernel='valu' covers up to 8 query heads per kv head, got 16")
     if not _paged_attention_kernel_ok(q, k_cache, B, Hq, Hk, D):
+        if kernel != "auto":
+            raise ValueError(f"kernel={kernel!r}: this call runs on the reference path (the kernels take CUDA bf16 "
+                             "tensors of paged_decode_supported shapes, 16-byte aligned)")
         return ref.paged_attention_decode_ref(q, k_cache, v_cache, block_table, context_lens, Hq, Hk, D, scale,
                                               k_scale, v_scale)
+    if kernel == "mfma" and G not in (8, 16):
+        raise ValueError(f"kernel='mfma' covers 8 or 16 query heads per kv head, got {G}")
+    mfma = kernel == "mfma" or (kernel == "auto" and (
+        G == 16 or (G == 8 and os.environ.get("RCA_ATTN_DECODE", "") == "mfma")))
     out = torch.empty(B, Hq * D, device=q.device, dtype=q.dtype)
     if B == 0:
         return out
@@ -1306,10 +1327,11 @@ def paged_attention_decode(q_or_qkv, k_cache, v_cache, block_table, context_lens
         # work on this stream)
         part_o = torch.empty(B, Hq, num_splits, D, device=q.device, dtype=torch.float32)
         part_ml = torch.empty(B, Hq, num_splits, 2, device=q.device, dtype=torch.float32)
-    check(L.rca_attn_decode_paged(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), _p(k_scale),
-                                  _p(v_scale), block_table.data_ptr(), context_lens.data_ptr(), out.data_ptr(),
-                                  _p(part_o), _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale,
-                                  num_splits, stream_ptr(q.device)), "rca_attn_decode_paged")
+    name = "rca_attn_decode_paged_mfma" if mfma else "rca_attn_decode_paged"
+    check(getattr(L, name)(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), _p(k_scale),
+                           _p(v_scale), block_table.data_ptr(), context_lens.data_ptr(), out.data_ptr(),
+                           _p(part_o), _p(part_ml), B, Hq, Hk, D, page, max_blocks, num_blocks, scale,
+                           num_splits, stream_ptr(q.device)), name)
     del part_o, part_ml
     return out
 

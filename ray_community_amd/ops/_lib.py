@@ -89,6 +89,9 @@ _SIGS = {
     "rca_attn_decode_paged": (c_int, [c_void_p, c_ll, *_KV,  # q, q_stride
         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,  # block_table, context_lens, out, part_o, part_ml
         c_int, c_int, c_int, c_int, *_TAIL]),  # B, Hq, Hk, D
+    "rca_attn_decode_paged_mfma": (c_int, [c_void_p, c_ll, *_KV,  # rca_attn_decode_paged's arguments
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+        c_int, c_int, c_int, c_int, *_TAIL]),
     "rca_attn_extend_paged": (c_int, [c_void_p, c_ll, *_KV,  # q, q_stride
         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,  # block_table, context_lens, cu_q_lens, out, part_o, part_ml
         c_int, c_ll, c_int, c_int, c_int, c_int, *_TAIL]),  # B, T, max_q_len, Hq, Hk, D

@@ -18,7 +18,8 @@
 // j < ceil(context_lens[b] / page_size), so NaN/Inf garbage in dead slots cannot reach the output.
 //
 // The entry points at the end, rca_kv_cache_append and rca_attn_decode_paged, serve both cache
-// kinds: the e4m3 kernels and their launchers are in attention_decode_fp8.hip (paged_kv.h).
+// kinds: the e4m3 kernels and their launchers are in attention_decode_fp8.hip (paged_kv.h). G = 16
+// decodes on the matrix unit (attention_decode_mfma.hip).
 #include "attention_combine.h"
 #include "attention_common.h"
 #include "paged_kv.h"
@@ -319,7 +320,9 @@ RCA_API int rca_kv_cache_append(const void* qkv, long long row_stride, const int
 // (Hq+2Hk)*D to read it in place from the fused qkv row). block_table: int32 [B, max_blocks];
 // context_lens: int32 [B]; caches and scales: either kind (paged_kv.h). out: bf16 [B, Hq*D].
 // num_splits > 1 needs part_o (fp32 [B, Hq, num_splits, D]) and part_ml (fp32 [B, Hq, num_splits, 2]
-// = (m, l)). D is 64 or 128, Hq / Hk one of 1, 2, 4, 8, page_size a multiple of 16.
+// = (m, l)). D is 64 or 128, Hq / Hk one of 1, 2, 4, 8, 16, page_size a multiple of 16. Hq / Hk up
+// to 8 runs the VALU kernels of this file and attention_decode_fp8.hip, 16 the MFMA kernel
+// (attention_decode_mfma.hip; rca_attn_decode_paged_mfma runs it for 8 as well).
 RCA_API int rca_attn_decode_paged(const void* q, long long q_stride, const void* k_cache, const void* v_cache,
                                   const void* k_scale, const void* v_scale, const int* block_table,
                                   const int* context_lens, void* out, void* part_o, void* part_ml, int B, int Hq,
@@ -330,7 +333,7 @@ RCA_API int rca_attn_decode_paged(const void* q, long long q_stride, const void*
   if (!paged_kv::grid_ok(B, Hk)) return -2;
   if (!paged_kv::caches_ok(k_cache, v_cache, k_scale, v_scale)) return -3;
   if (!paged_kv::attn_ptrs_ok(q, out, block_table, context_lens, part_o, part_ml, num_splits)) return -3;
-  return (k_scale ? launch_attn_decode_fp8 : launch_attn_decode_bf16)(
+  return (Hq / Hk == 16 ? launch_attn_decode_mfma : k_scale ? launch_attn_decode_fp8 : launch_attn_decode_bf16)(
       q, q_stride, k_cache, v_cache, k_scale, v_scale, block_table, context_lens, out, part_o, part_ml, B, Hq, Hk, D,
       page_size, max_blocks, num_blocks, scale, num_splits, stream);
 }

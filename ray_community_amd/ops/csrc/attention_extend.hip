@@ -322,10 +322,12 @@ RCA_EXT_INST(64, 1)
 RCA_EXT_INST(64, 2)
 RCA_EXT_INST(64, 4)
 RCA_EXT_INST(64, 8)
+RCA_EXT_INST(64, 16)
 RCA_EXT_INST(128, 1)
 RCA_EXT_INST(128, 2)
 RCA_EXT_INST(128, 4)
 RCA_EXT_INST(128, 8)
+RCA_EXT_INST(128, 16)
 #undef RCA_EXT_INST
 #undef RCA_EXT_INST1
 
@@ -360,7 +362,7 @@ int launch_attn_extend_bf16(const void* q, long long q_stride, const void* k_cac
                             int D, int page_size, int max_blocks, int num_blocks, float scale, int num_splits,
                             unsigned tiles, hipStream_t stream) {
   const int rc = with_bool(num_splits > 1, [&](auto split) {
-    return paged_kv::dispatch_dg(D, Hq / Hk, [&](auto d, auto g) {
+    return paged_kv::dispatch_dg16(D, Hq / Hk, [&](auto d, auto g) {
       hipLaunchKernelGGL((attn_extend_paged_kernel<d.value, g.value, split.value>), dim3(tiles, Hk, B),
                          dim3(kThreads), 0, stream, (const bf16_t*)q, (long)q_stride, (const bf16_t*)k_cache,
                          (const bf16_t*)v_cache, block_table, context_lens, cu_q_lens, (bf16_t*)out, max_q_len, Hk,
@@ -378,7 +380,9 @@ int launch_attn_extend_bf16(const void* q, long long q_stride, const void* k_cac
 // contiguous q, (Hq+2Hk)*D to read it in place from the fused qkv row). cu_q_lens: int32 [B+1],
 // non-decreasing, cu_q_lens[B] <= T = rows of q and out; max_q_len >= every chunk length (host side:
 // it sizes the grid). context_lens counts each sequence's cached tokens including its chunk. Caches
-// and scales: either kind (paged_kv.h). out: bf16 [T, Hq*D]. scale must be > 0.
+// and scales: either kind (paged_kv.h). out: bf16 [T, Hq*D]. scale must be > 0. D is 64 or 128,
+// Hq / Hk one of 1, 2, 4, 8, 16 (the kernels' G is index arithmetic only: row / G, row % G), page_size
+// a multiple of 16.
 //
 // num_splits == 1 is the unsplit launch: no workspace, T unread, rows of out that no sequence owns
 // not written. num_splits > 1 runs that many splits of every row tile's keys, merged in split order

@@ -354,10 +354,12 @@ RCA_EXT_INST(64, 1)
 RCA_EXT_INST(64, 2)
 RCA_EXT_INST(64, 4)
 RCA_EXT_INST(64, 8)
+RCA_EXT_INST(64, 16)
 RCA_EXT_INST(128, 1)
 RCA_EXT_INST(128, 2)
 RCA_EXT_INST(128, 4)
 RCA_EXT_INST(128, 8)
+RCA_EXT_INST(128, 16)
 #undef RCA_EXT_INST
 #undef RCA_EXT_INST1
 
@@ -370,7 +372,7 @@ int launch_attn_extend_fp8(const void* q, long long q_stride, const void* k_cach
                            int max_q_len, int Hq, int Hk, int D, int page_size, int max_blocks, int num_blocks,
                            float scale, int num_splits, unsigned tiles, hipStream_t stream) {
   const int rc = with_bool(num_splits > 1, [&](auto split) {
-    return paged_kv::dispatch_dg(D, Hq / Hk, [&](auto d, auto g) {
+    return paged_kv::dispatch_dg16(D, Hq / Hk, [&](auto d, auto g) {
       hipLaunchKernelGGL((attn_extend_paged_fp8_kernel<d.value, g.value, split.value>), dim3(tiles, Hk, B),
                          dim3(kThreads), 0, stream, (const bf16_t*)q, (long)q_stride, (const fp8_t*)k_cache,
                          (const fp8_t*)v_cache, (const float*)k_scale, (const float*)v_scale, block_table,

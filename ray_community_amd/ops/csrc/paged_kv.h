@@ -64,22 +64,37 @@ constexpr float kLog2e = 1.44269504088896340736f;  // the kernels' softmax is ba
 
 // Host dispatch: run-time D in {64, 128} and G in {1, 2, 4, 8} -> compile-time ones. f receives
 // std::integral_constant values (use ``d.value`` / ``g.value`` as template arguments) and returns
-// int; -1 for a G no kernel is instantiated for. The caller has checked D.
+// int; -1 for a G no kernel is instantiated for. The caller has checked D. dispatch_dg is the VALU
+// decode kernels' (G accumulator rows per lane: 8 is their limit; G = 16 decodes on the MFMA kernel,
+// attention_decode_mfma.hip, which takes G at run time); dispatch_dg16 adds G = 16 for the extend
+// kernels, whose G is index arithmetic only.
 template <int N>
 using int_c = std::integral_constant<int, N>;
 
-template <typename F>
-int dispatch_dg(int D, int G, F&& f) {
+template <bool G16, typename F>
+int dispatch_dg_upto(int D, int G, F&& f) {
   auto with_d = [&](auto d) {
     switch (G) {
       case 1: return f(d, int_c<1>{});
       case 2: return f(d, int_c<2>{});
       case 4: return f(d, int_c<4>{});
       case 8: return f(d, int_c<8>{});
+      case 16:
+        if constexpr (G16) return f(d, int_c<16>{});
     }
     return -1;
   };
   return D == 128 ? with_d(int_c<128>{}) : with_d(int_c<64>{});
+}
+
+template <typename F>
+int dispatch_dg(int D, int G, F&& f) {
+  return dispatch_dg_upto<false>(D, G, f);
+}
+
+template <typename F>
+int dispatch_dg16(int D, int G, F&& f) {
+  return dispatch_dg_upto<true>(D, G, f);
 }
 
 }  // namespace paged_kv
@@ -102,6 +117,8 @@ using attn_decode_launcher = int(const void* q, long long q_stride, const void* 
                                  int Hk, int D, int page_size, int max_blocks, int num_blocks, float scale,
                                  int num_splits, hipStream_t stream);
 RCA_LOCAL attn_decode_launcher launch_attn_decode_bf16, launch_attn_decode_fp8;
+// the MFMA decode for G <= 16 (attention_decode_mfma.hip): either cache kind, told by the scales
+RCA_LOCAL attn_decode_launcher launch_attn_decode_mfma;
 
 // the same for the extend; `tiles` is the grid's x dimension, T is read only when num_splits > 1
 using attn_extend_launcher = int(const void* q, long long q_stride, const void* k_cache, const void* v_cache,

@@ -13,6 +13,13 @@ End to end: ``Llama.generate`` tokens/s for llama3-1b at batch 1 and batch 32.
 on the same K/V, interleaved in one process, at the shape above, at G = 8 and at B=1 with context
 32768 (us, effective KV TB/s, the bf16 arm's min-max), and ``generate`` tokens/s at batch 32 with
 both cache dtypes.
+
+``--kernel {auto,valu,mfma}`` is ``ops.paged_attention_decode``'s ``kernel`` for the HIP arms above
+(shapes with 16 query heads per kv head run with ``auto`` or ``mfma``). ``--mfma-ab`` measures the
+MFMA decode kernel (``ops/csrc/attention_decode_mfma.hip``) against what ran before it, arms
+interleaved in one process, bf16 and fp8 caches: at G = 8 (Hq=64) the VALU kernel, at G = 16
+(Hq=128) ``ops.reference``; B=32 at context 4096 and one sequence of 32768 tokens
+(profiles/decode_attention_mfma.md).
 """
 import argparse
 import json
@@ -27,6 +34,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from ray_community_amd import ops  # noqa: E402
+from ray_community_amd.ops import reference  # noqa: E402
 from ray_community_amd.models import build_llama  # noqa: E402
 
 
@@ -40,7 +48,7 @@ def _time(fn, iters):
     return start.elapsed_time(end) * 1e3 / iters  # us
 
 
-def kernel_bench(rounds, iters, B=32, ctx=4096, Hq=32, Hk=8, D=128, page=16, num_splits=None):
+def kernel_bench(rounds, iters, B=32, ctx=4096, Hq=32, Hk=8, D=128, page=16, num_splits=None, kernel="auto"):
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
     pages = ctx // page
@@ -56,7 +64,8 @@ def kernel_bench(rounds, iters, B=32, ctx=4096, Hq=32, Hk=8, D=128, page=16, num
     q4 = q.view(B, Hq, 1, D)
 
     def hip():
-        return ops.paged_attention_decode(q, k_cache, v_cache, table, lens, Hq, Hk, D, num_splits=num_splits)
+        return ops.paged_attention_decode(q, k_cache, v_cache, table, lens, Hq, Hk, D, num_splits=num_splits,
+                                          kernel=kernel)
 
     def sdpa():
         return F.scaled_dot_product_attention(q4, kg, vg, enable_gqa=True)
@@ -158,6 +167,67 @@ def fp8_kernel_bench(rounds, iters, B=32, ctx=4096, Hq=32, Hk=8, D=128, page=16)
     return res
 
 
+def mfma_ab_bench(rounds, iters, B=32, ctx=4096, Hq=64, Hk=8, D=128, page=16, fp8=False):
+    """``kernel="mfma"`` against the VALU kernel (G = 8) or the reference path (G = 16: what ran
+    before the MFMA kernel; one call per round, it takes milliseconds) on the same caches,
+    interleaved round by round. KV bytes as in ``fp8_kernel_bench``."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    pages = ctx // page
+    num_blocks = B * pages
+    W = (Hq + 2 * Hk) * D
+    kc = torch.empty(num_blocks, page, Hk, D, device=dev, dtype=torch.float8_e4m3fn if fp8 else torch.bfloat16)
+    vc = torch.empty_like(kc)
+    sc = dict(k_scale=torch.empty(num_blocks, page, Hk, device=dev, dtype=torch.float32),
+              v_scale=torch.empty(num_blocks, page, Hk, device=dev, dtype=torch.float32)) if fp8 else {}
+    rows = 2048
+    for s0 in range(0, num_blocks * page, rows):  # fill the caches through the append kernel
+        n = min(rows, num_blocks * page - s0)
+        qkv = torch.randn(n, W, device=dev, dtype=torch.bfloat16, generator=g)
+        ops.kv_cache_append_(kc, vc, qkv, torch.arange(s0, s0 + n, device=dev, dtype=torch.int32), Hq, Hk, D, **sc)
+    table = torch.randperm(num_blocks, device=dev, generator=g).to(torch.int32).view(B, pages)
+    lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    q = torch.randn(B, Hq * D, device=dev, dtype=torch.bfloat16, generator=g)
+
+    def mfma():
+        return ops.paged_attention_decode(q, kc, vc, table, lens, Hq, Hk, D, kernel="mfma", **sc)
+
+    def valu():
+        return ops.paged_attention_decode(q, kc, vc, table, lens, Hq, Hk, D, kernel="valu", **sc)
+
+    def ref():
+        return reference.paged_attention_decode_ref(q, kc, vc, table, lens, Hq, Hk, D, D ** -0.5, *sc.values())
+
+    other, fn, n_other = ("valu", valu, iters) if Hq // Hk <= 8 else ("reference", ref, 1)
+    a, b = mfma().float(), fn().float()
+    diff = ((a - b).abs().amax(-1) / b.abs().amax(-1)).max().item()
+    times = {"mfma": [], other: []}
+    for _ in range(3):  # warm-up
+        _time(mfma, iters)
+        _time(fn, n_other)
+    for _ in range(rounds):  # interleaved arms
+        times["mfma"].append(_time(mfma, iters))
+        times[other].append(_time(fn, n_other))
+    nbytes = 2 * B * ctx * Hk * (D + 4) if fp8 else 2 * B * ctx * Hk * D * 2
+    res = {"shape": dict(B=B, ctx=ctx, Hq=Hq, Hk=Hk, D=D, page=page), "cache": "fp8" if fp8 else "bf16",
+           "num_splits": ops.lib().rca_attn_decode_num_splits(B, Hk, ctx, page), f"mfma_vs_{other}_row_diff": diff}
+    for k, t in times.items():
+        us = statistics.median(t)
+        res[k] = {"us": round(us, 2), "us_min_max": [round(min(t), 2), round(max(t), 2)],
+                  "kv_TBps": round(nbytes / us / 1e6, 3)}
+    res[f"mfma_over_{other}_time"] = round(res["mfma"]["us"] / res[other]["us"], 3)
+    return res
+
+
+def mfma_ab_main(args):
+    res = []
+    for fp8 in (False, True):
+        for shape in (dict(Hq=64), dict(Hq=128), dict(Hq=64, B=1, ctx=32768), dict(Hq=128, B=1, ctx=32768)):
+            res.append(mfma_ab_bench(args.rounds, args.iters, fp8=fp8, **shape))
+            print(json.dumps(res[-1]), flush=True)
+    return {"mfma_ab": res}
+
+
 def fp8_e2e_bench(batch=32, prompt_len=128, new_tokens=64, reps=3):
     """``generate`` tokens/s on llama3-1b with both cache dtypes, repetitions interleaved."""
     torch.manual_seed(0)
@@ -200,11 +270,24 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the fp8-cache kernels against the bf16-cache ones, both arms in this process")
+    ap.add_argument("--kernel", choices=["auto", "valu", "mfma"], default="auto",
+                    help="ops.paged_attention_decode's kernel for the bf16 kernel timings")
+    ap.add_argument("--hq", type=int, default=None, help="query heads of the bf16 kernel timings (Hk = 8): "
+                    "64 for G = 8, 128 for G = 16; default 32, then 64")
+    ap.add_argument("--mfma-ab", action="store_true", help="the MFMA decode kernel against the VALU kernel (G = 8) "
+                    "and the reference path (G = 16), both caches")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("decode_bench.py needs a GPU")
-    if args.kv_dtype == "fp8":
-        res = fp8_main(args)
+    if args.mfma_ab or args.kv_dtype == "fp8":
+        res = mfma_ab_main(args) if args.mfma_ab else fp8_main(args)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
+    if args.hq is not None or args.kernel != "auto":  # one shape on the named kernel
+        res = {"kernel": kernel_bench(args.rounds, args.iters, Hq=args.hq or 64, kernel=args.kernel)}
+        print(json.dumps(res["kernel"]), flush=True)
         if args.json:
             with open(args.json, "w") as f:
                 json.dump(res, f, indent=1)
