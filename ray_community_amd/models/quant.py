@@ -2,10 +2,12 @@
 
 ``"fp8"``: a quantised linear holds its weight as OCP e4m3 bytes ``[out, in]`` plus one power-of-two
 fp32 scale per output row (``ops.reference.quantize_weight_fp8_ref``), half the bytes of bf16, and runs
-``ops.linear_w8``: the W8A16 kernel at decode batch sizes, dequantise + ``F.linear`` for prefill.
+``ops.linear_w8``: the W8A16 skinny kernel up to ``ops.M_SKINNY`` rows, the mid-M kernel up to
+``ops.M_MID`` (many live slots, a speculative verify round, a short prefill chunk; the same bits per row
+as the skinny kernel, whatever the batch), dequantise + ``F.linear`` for longer prefill.
 ``"mxfp4"``: OCP microscaling FP4, two e2m1 nibbles a byte ``[out, in/2]`` plus one E8M0 scale byte per
 32 inputs ``[out, in/32]`` (``ops.reference.quantize_weight_mxfp4_ref``), 4.25 bits a weight, through
-``ops.linear_w4`` in the same way.
+``ops.linear_w4`` in the same way (``ops.M_SKINNY_W4``, ``ops.M_MID_W4``).
 Activations stay bf16. Quantisation happens once, in torch, after the weights are loaded.
 """
 from __future__ import annotations

@@ -1660,6 +1660,22 @@ def token_logprobs(logits, tokens, top_n=0):
 # row tile (one stream of the weight) and the largest measured M at which the kernel beats the bf16 arm
 # on every llama3-8b shape (at M = 64 it loses on gate_up and lm_head): profiles/weight_fp8.md.
 M_SKINNY = 32
+# Rows up to which ``linear_w8`` stays in HIP above ``M_SKINNY``: the mid-M kernel (ops/csrc/linear_mid.h:
+# the weight streamed and converted once per 128 rows, bit for bit the skinny kernel's output). The
+# largest M of the grid 33 .. 1024 up to which the kernel is no slower than dequantise + ``F.linear`` on
+# every llama3-8b shape: profiles/weight_mid_m.md.
+M_MID = 128
+
+_LINEAR_KERNELS = ("auto", "skinny", "mid", "dequant")
+
+
+def _linear_arm(kernel: str, M: int, m_skinny: int, m_mid: int) -> str:
+    """The arm of ``linear_w8`` / ``linear_w4`` for M rows: the forced one, or by the two thresholds."""
+    if kernel not in _LINEAR_KERNELS:
+        raise ValueError(f"kernel must be one of {_LINEAR_KERNELS}, got {kernel!r}")
+    if kernel != "auto":
+        return kernel
+    return "skinny" if M <= m_skinny else "mid" if M <= m_mid else "dequant"
 
 
 def _w8_tensor_ok(t) -> bool:
@@ -1679,14 +1695,15 @@ def linear_w8_supported(M: int, N: int, K: int, *tensors) -> bool:
     return M >= 1 and N > 0 and K > 0 and N % 16 == 0 and K % 128 == 0 and all(_w8_tensor_ok(t) for t in tensors)
 
 
-def _linear_w8_kernel(x2, qweight, scale, out):
-    """The kernel launch on operands ``linear_w8_supported`` accepts, whatever M is."""
+def _linear_w8_kernel(x2, qweight, scale, out, mid=False):
+    """The skinny (or, ``mid``, the mid-M) kernel launch on operands ``linear_w8_supported`` accepts,
+    whatever M is."""
     M, K = x2.shape
     N = qweight.shape[0]
     L = lib()
     splits = L.rca_linear_w8_splits(N, K)
     ws = _workspace(x2.device, "linear_w8_split", splits * M * N) if splits > 1 else None
-    check(L.rca_linear_w8a16(x2.data_ptr(), qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), _p(ws),
+    check((L.rca_linear_w8a16_mid if mid else L.rca_linear_w8a16)(x2.data_ptr(), qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), _p(ws),
                              ws.numel() * 4 if ws is not None else 0, M, N, K, x2.stride(0), out.stride(0),
                              stream_ptr(x2.device)), "linear_w8a16")
     return out
@@ -1711,7 +1728,7 @@ def dequant_w8(qweight, scale, out=None):
     return out
 
 
-def linear_w8(x, qweight, scale, out=None):
+def linear_w8(x, qweight, scale, out=None, kernel="auto"):
     """``x [..., K] @ (qweight [N, K] * scale [N]).T`` for an fp8-quantised weight
     (``reference.quantize_weight_fp8_ref``: e4m3 bytes, held as ``float8_e4m3fn`` or ``uint8``, and
     one power-of-two fp32 scale per output row). No autograd: inference only.
@@ -1719,10 +1736,16 @@ def linear_w8(x, qweight, scale, out=None):
     bf16 CUDA ``x`` within ``linear_w8_supported``: up to ``M_SKINNY`` rows run the W8A16 kernel
     (the weight is streamed as bytes, converted to bf16 in registers, accumulated in fp32 on the
     MFMA, scaled and rounded once; an output row depends on its own input row only, not on the batch
-    it came in). More rows (prefill) dequantise the weight into one per-device bf16 workspace on
-    the current stream and call ``F.linear``. An ``x`` with a non-unit inner stride or a misaligned
-    base is made contiguous first. CPU tensors, other dtypes and shapes outside the contract run
-    ``reference.linear_w8_ref``. ``out``: a bf16 ``[M, N]`` tensor or view to write."""
+    it came in). Up to ``M_MID`` rows run the mid-M kernel (the weight streamed and converted once
+    per 128 rows; the same sums in the same order, so a row's bits are those of the skinny kernel
+    whatever the batch). More rows (prefill) dequantise the weight into one per-device bf16
+    workspace on the current stream and call ``F.linear``. An ``x`` with a non-unit inner stride or
+    a misaligned base is made contiguous first. CPU tensors, other dtypes and shapes outside the
+    contract run ``reference.linear_w8_ref``. ``out``: a bf16 ``[M, N]`` tensor or view to write.
+
+    ``kernel``: ``"auto"`` (by M, as above), or ``"skinny"`` / ``"mid"`` / ``"dequant"`` to run that
+    arm at any ``M >= 1``; a forced arm never falls back: a call that would run the reference
+    raises ``ValueError``."""
     if qweight.dtype == torch.uint8:
         qweight = qweight.view(torch.float8_e4m3fn)
     N, K = qweight.shape
@@ -1736,12 +1759,15 @@ def linear_w8(x, qweight, scale, out=None):
         raise ValueError(f"linear_w8: out must be a {x.dtype} [{M}, {N}] tensor on {x.device}")
     if x2.is_cuda and x2.dtype == torch.bfloat16 and not _w8_tensor_ok(x2):
         x2 = x2.contiguous()
+    arm = _linear_arm(kernel, M, M_SKINNY, M_MID)
     if not linear_w8_supported(M, N, K, x2, qweight, scale):
+        if kernel != "auto":
+            raise ValueError(f"linear_w8: kernel={kernel!r} needs bf16 CUDA operands within linear_w8_supported")
         y = ref.linear_w8_ref(x2, qweight, scale)
-    elif M <= M_SKINNY:
+    elif arm != "dequant":
         direct = out is not None and _w8_tensor_ok(out)
         y = _linear_w8_kernel(x2, qweight, scale,
-                              out if direct else torch.empty((M, N), device=x.device, dtype=torch.bfloat16))
+                              out if direct else torch.empty((M, N), device=x.device, dtype=torch.bfloat16), mid=arm == "mid")
         if direct:
             return out
     else:
@@ -1759,6 +1785,10 @@ def linear_w8(x, qweight, scale, out=None):
 # row tile (one stream of the weight) and the largest measured M at which the kernel beats the bf16 arm
 # on every llama3-8b shape (at M = 64 it loses on gate_up): profiles/weight_mxfp4.md.
 M_SKINNY_W4 = 32
+# Rows up to which ``linear_w4`` stays in HIP above ``M_SKINNY_W4`` (the mid-M kernel, as ``M_MID``): the
+# largest M of the grid 33 .. 1024 up to which it is no slower than dequantise + ``F.linear`` on every
+# llama3-8b shape: profiles/weight_mid_m.md.
+M_MID_W4 = 256
 
 
 def _w4_tensor_ok(t) -> bool:
@@ -1772,14 +1802,15 @@ def linear_w4_supported(M: int, N: int, K: int, *tensors) -> bool:
     return M >= 1 and N > 0 and K > 0 and N % 16 == 0 and K % 256 == 0 and all(_w4_tensor_ok(t) for t in tensors)
 
 
-def _linear_w4_kernel(x2, qweight, scale, out):
-    """The kernel launch on operands ``linear_w4_supported`` accepts, whatever M is."""
+def _linear_w4_kernel(x2, qweight, scale, out, mid=False):
+    """The skinny (or, ``mid``, the mid-M) kernel launch on operands ``linear_w4_supported`` accepts,
+    whatever M is."""
     M, K = x2.shape
     N = qweight.shape[0]
     L = lib()
     splits = L.rca_linear_w4_splits(N, K)
     ws = _workspace(x2.device, "linear_w4_split", splits * M * N) if splits > 1 else None
-    check(L.rca_linear_w4a16(x2.data_ptr(), qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), _p(ws),
+    check((L.rca_linear_w4a16_mid if mid else L.rca_linear_w4a16)(x2.data_ptr(), qweight.data_ptr(), scale.data_ptr(), out.data_ptr(), _p(ws),
                              ws.numel() * 4 if ws is not None else 0, M, N, K, x2.stride(0), out.stride(0),
                              stream_ptr(x2.device)), "linear_w4a16")
     return out
@@ -1811,7 +1842,7 @@ def dequant_w4(qweight, scale, out=None):
     return out
 
 
-def linear_w4(x, qweight, scale, out=None):
+def linear_w4(x, qweight, scale, out=None, kernel="auto"):
     """``x [..., K] @ deq(qweight, scale).T`` for an MXFP4-quantised weight
     (``reference.quantize_weight_mxfp4_ref``: ``uint8 [N, K/2]`` e2m1 nibble pairs, the low nibble the
     even ``k``, and ``uint8 [N, K/32]`` E8M0 block scales, any value in ``[2, 252]``). No autograd:
@@ -1820,11 +1851,17 @@ def linear_w4(x, qweight, scale, out=None):
     bf16 CUDA ``x`` within ``linear_w4_supported``: up to ``M_SKINNY_W4`` rows run the W4A16 kernel
     (the weight is streamed as nibbles, converted to bf16 in registers with its block scale applied,
     accumulated in fp32 on the MFMA and rounded once; an output row depends on its own input row
-    only, not on the batch it came in). More rows (prefill) dequantise the weight into one
-    per-device bf16 workspace on the current stream and call ``F.linear``. An ``x`` with a non-unit
-    inner stride or a misaligned base is made contiguous first. CPU tensors, other dtypes and shapes
-    outside the contract run ``reference.linear_w4_ref``. ``out``: a bf16 ``[M, N]`` tensor or view
-    to write."""
+    only, not on the batch it came in). Up to ``M_MID_W4`` rows run the mid-M kernel (the weight
+    streamed and converted once per 128 rows; the same sums in the same order, so a row's bits are
+    those of the skinny kernel whatever the batch). More rows (prefill) dequantise the weight into
+    one per-device bf16 workspace on the current stream and call ``F.linear``. An ``x`` with a
+    non-unit inner stride or a misaligned base is made contiguous first. CPU tensors, other dtypes
+    and shapes outside the contract run ``reference.linear_w4_ref``. ``out``: a bf16 ``[M, N]``
+    tensor or view to write.
+
+    ``kernel``: ``"auto"`` (by M, as above), or ``"skinny"`` / ``"mid"`` / ``"dequant"`` to run that
+    arm at any ``M >= 1``; a forced arm never falls back: a call that would run the reference
+    raises ``ValueError``."""
     N, K = _check_w4("linear_w4", qweight, scale)
     if x.shape[-1] != K:
         raise ValueError(f"linear_w4: x [..., {x.shape[-1]}] and qweight [{N}, {K}/2] do not agree")
@@ -1835,12 +1872,15 @@ def linear_w4(x, qweight, scale, out=None):
         raise ValueError(f"linear_w4: out must be a {x.dtype} [{M}, {N}] tensor on {x.device}")
     if x2.is_cuda and x2.dtype == torch.bfloat16 and not _w8_tensor_ok(x2):
         x2 = x2.contiguous()
+    arm = _linear_arm(kernel, M, M_SKINNY_W4, M_MID_W4)
     if not linear_w4_supported(M, N, K, x2, qweight, scale):
+        if kernel != "auto":
+            raise ValueError(f"linear_w4: kernel={kernel!r} needs bf16 CUDA operands within linear_w4_supported")
         y = ref.linear_w4_ref(x2, qweight, scale)
-    elif M <= M_SKINNY_W4:
+    elif arm != "dequant":
         direct = out is not None and _w4_tensor_ok(out)
         y = _linear_w4_kernel(x2, qweight, scale,
-                              out if direct else torch.empty((M, N), device=x.device, dtype=torch.bfloat16))
+                              out if direct else torch.empty((M, N), device=x.device, dtype=torch.bfloat16), mid=arm == "mid")
         if direct:
             return out
     else:

@@ -31,12 +31,15 @@
 // order by a second kernel (no atomics): an output row is a function of its own x row and W, whatever
 // M is and wherever the row sits in the batch. Rows of a 16-row MFMA tile beyond M are zeros in LDS and
 // are not stored; a column of the MFMA result depends on its own column operand only.
+//
+// Mid M (33 .. ops.M_MID_W4 rows): linear_mid.h's loop with the producer below, the same K ranges, the same
+// k-set and order per MFMA and the same combine kernel, so its output equals this kernel's bit for bit.
 #include "common.h"
-#include "w4_cvt.h"  // w4_cvt8, e8m0
+#include "linear_mid.h"  // bf16x8_t, lds_barrier, linear_mid_launch
+#include "w4_cvt.h"      // w4_cvt8, e8m0
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kBN = 64;               // output columns per block: 4 waves x one 16-wide MFMA tile
@@ -46,12 +49,6 @@ constexpr int kRowB = kKT * 2 + 16;   // LDS bytes per x row: +16 so the 16 m-la
 constexpr int kMinSplitChunks = 4;    // a K range is at least 4 x 256 deep
 constexpr int kMaxSplits = 8;
 constexpr int kTargetBlocks = 512;    // two blocks per CU
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 template <int MT, bool SPLIT>
 __global__ __launch_bounds__(256) void linear_w4a16_kernel(const bf16_t* __restrict__ x, long long ldx,
@@ -178,6 +175,39 @@ __global__ __launch_bounds__(256) void linear_w4a16_kernel(const bf16_t* __restr
   }
 }
 
+// linear_mid.h's weight producer: a chunk is one 128-byte line of a weight row and its 8 scale bytes. Lane
+// (n, g) holds bytes 16 (4 h + g) ..+15 of the line for h = 0, 1 (MX block 4 h + g: one scale, byte 4 h + g)
+// and MFMA s = 4 h + j takes dword j of load h: the skinny kernel's fragments.
+struct W4Producer {
+  static constexpr int kCK = 256;  // the skinny kernel's chunk
+  static constexpr bool kRowScale = false;
+  const unsigned char* W;
+  const unsigned char* E;
+  struct Row {
+    const unsigned char *w, *e;
+  };
+  struct Raw {
+    u32x4 w[2];
+    uint2 e;
+  };
+  __device__ __forceinline__ Row row(size_t n, int K, int g) const {
+    return Row{W + n * (size_t)(K / 2) + g * 16, E + n * (size_t)(K / 32)};
+  }
+  static __device__ __forceinline__ void load(Raw& r, const Row& row, int k, bool in) {
+    r.e = make_uint2(0u, 0u);
+    r.w[0] = r.w[1] = u32x4{0u, 0u, 0u, 0u};
+    if (in) {
+      r.e = *reinterpret_cast<const uint2*>(row.e + k / 32);
+      r.w[0] = *reinterpret_cast<const u32x4*>(row.w + k / 2);
+      r.w[1] = *reinterpret_cast<const u32x4*>(row.w + k / 2 + 64);
+    }
+  }
+  static __device__ __forceinline__ bf16x8_t frag(const Raw& r, int s, int g) {
+    const float sc = e8m0((((s >> 2) ? r.e.y : r.e.x) >> (8 * g)) & 0xffu);
+    return __builtin_bit_cast(bf16x8_t, w4_cvt8(r.w[s >> 2][s & 3], sc));
+  }
+};
+
 // y[m][n..n+3] = bf16(part[0] + part[1] + ... in range order)
 __global__ __launch_bounds__(256) void linear_w4_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ y,
                                                                 long long ldy, int M, int N, int splits) {
@@ -218,6 +248,18 @@ int w4_splits(int N, int K) {
 
 bool w4_shape_ok(int N, int K) { return N > 0 && K > 0 && N % 16 == 0 && K % kCK == 0; }
 
+// the argument checks of both linear entries (0: take the call) and the K ranges: `per` chunks in each of `splits`
+int w4_check(const void* x, const void* wq, const void* scale, const void* y, const void* ws, long long ws_bytes, int M,
+             int N, int K, long long ldx, long long ldy, int& splits, int& per) {
+  if (!w4_shape_ok(N, K) || M < 1 || (M + 31) / 32 > 65535) return -1;
+  if ((ldx | ldy) & 7 || ldx < K || ldy < N) return -2;
+  if (((uintptr_t)x | (uintptr_t)wq | (uintptr_t)scale | (uintptr_t)y) & 15) return -2;
+  splits = w4_splits(N, K);
+  per = (K / kCK + splits - 1) / splits;
+  if (splits > 1 && (!ws || ((uintptr_t)ws & 15) || ws_bytes < (long long)splits * M * N * 4)) return -3;
+  return 0;
+}
+
 }  // namespace
 
 // K ranges rca_linear_w4a16 uses for an [N][K] weight (a function of N and K only); 0: outside the contract
@@ -228,11 +270,8 @@ RCA_API int rca_linear_w4_splits(int N, int K) { return w4_shape_ok(N, K) ? w4_s
 // -1: shape outside the contract (K % 256, N % 16, M >= 1); -2: alignment / stride; -3: workspace; -4: launch.
 RCA_API int rca_linear_w4a16(const void* x, const void* wq, const void* scale, void* y, void* ws, long long ws_bytes,
                              int M, int N, int K, long long ldx, long long ldy, hipStream_t st) {
-  if (!w4_shape_ok(N, K) || M < 1 || (M + 31) / 32 > 65535) return -1;
-  if ((ldx | ldy) & 7 || ldx < K || ldy < N) return -2;
-  if (((uintptr_t)x | (uintptr_t)wq | (uintptr_t)scale | (uintptr_t)y) & 15) return -2;
-  const int splits = w4_splits(N, K), chunks = K / kCK, per = (chunks + splits - 1) / splits;
-  if (splits > 1 && (!ws || ((uintptr_t)ws & 15) || ws_bytes < (long long)splits * M * N * 4)) return -3;
+  int splits, per;
+  if (const int rc = w4_check(x, wq, scale, y, ws, ws_bytes, M, N, K, ldx, ldy, splits, per)) return rc;
   const bool one = M <= 16;
   const dim3 grid((N + kBN - 1) / kBN, one ? 1 : (M + 31) / 32, splits);
   const bf16_t* xp = (const bf16_t*)x;
@@ -251,6 +290,22 @@ RCA_API int rca_linear_w4a16(const void* x, const void* wq, const void* scale, v
     linear_w4a16_kernel<1, false><<<grid, 256, 0, st>>>(xp, ldx, wp, ep, yp, ldy, pp, M, N, K, per);
   } else {
     linear_w4a16_kernel<2, false><<<grid, 256, 0, st>>>(xp, ldx, wp, ep, yp, ldy, pp, M, N, K, per);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// rca_linear_w4a16 for the rows above its tile (arguments, return codes and workspace rule are its own; any
+// M >= 1 is taken): the weight is streamed and converted once per 128 rows of x (linear_mid.h). Bit for bit
+// rca_linear_w4a16's output.
+RCA_API int rca_linear_w4a16_mid(const void* x, const void* wq, const void* scale, void* y, void* ws,
+                                 long long ws_bytes, int M, int N, int K, long long ldx, long long ldy, hipStream_t st) {
+  int splits, per;
+  if (const int rc = w4_check(x, wq, scale, y, ws, ws_bytes, M, N, K, ldx, ldy, splits, per)) return rc;
+  const W4Producer p{(const unsigned char*)wq, (const unsigned char*)scale};
+  if (!linear_mid_launch((const bf16_t*)x, ldx, p, (bf16_t*)y, ldy, (float*)ws, M, N, K, splits, per, st)) return -4;
+  if (splits > 1) {
+    const long long quads = (long long)M * (N / 4);
+    linear_w4_combine_kernel<<<(unsigned)((quads + 255) / 256), 256, 0, st>>>((float*)ws, (bf16_t*)y, ldy, M, N, splits);
   }
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }

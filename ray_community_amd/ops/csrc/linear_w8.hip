@@ -24,11 +24,14 @@
 // atomics): an output row is a function of its own x row and W, whatever M is and wherever the row
 // sits in the batch. Rows of a 16-row MFMA tile beyond M are zeros in LDS and are not stored; a column
 // of the MFMA result depends on its own column operand only.
+//
+// Mid M (33 .. ops.M_MID rows): linear_mid.h's loop with the producer below, the same K ranges, the same
+// k-set and order per MFMA, the same epilogue and combine kernel, so its output equals this kernel's bit
+// for bit.
 #include "kv_fp8.h"
+#include "linear_mid.h"  // bf16x8_t, lds_barrier, linear_mid_launch
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int kBN = 64;               // output columns per block: 4 waves x one 16-wide MFMA tile
 constexpr int kKT = 256;              // k per LDS stage
@@ -36,12 +39,6 @@ constexpr int kRowB = kKT * 2 + 16;   // LDS bytes per x row: +16 so the 16 m-la
 constexpr int kMinSplitBlocks = 4;    // a K range is at least 4 x 128 deep
 constexpr int kMaxSplits = 8;
 constexpr int kTargetBlocks = 512;    // two blocks per CU
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // 8 e4m3 bytes -> the bf16 MFMA fragment (exact)
 __device__ __forceinline__ bf16x8_t w8_frag(unsigned lo, unsigned hi) {
@@ -162,6 +159,32 @@ __global__ __launch_bounds__(256) void linear_w8a16_kernel(const bf16_t* __restr
   }
 }
 
+// linear_mid.h's weight producer: a chunk is one 128-byte line of a weight row, of which lane (n, g) holds
+// bytes 32 g ..+31 (two 16-byte loads); MFMA s takes bytes 8 s ..+7 of them: the skinny kernel's fragments.
+struct W8Producer {
+  static constexpr int kCK = 128;
+  static constexpr bool kRowScale = true;
+  const fp8_t* W;
+  const float* s;
+  typedef const fp8_t* Row;
+  struct Raw {
+    u32x4 w[2];
+  };
+  __device__ __forceinline__ Row row(size_t n, int K, int g) const { return W + n * (size_t)K + g * 32; }
+  static __device__ __forceinline__ void load(Raw& r, Row row, int k, bool in) {
+    r.w[0] = r.w[1] = u32x4{0u, 0u, 0u, 0u};
+    if (in) {
+      r.w[0] = *reinterpret_cast<const u32x4*>(row + k);
+      r.w[1] = *reinterpret_cast<const u32x4*>(row + k + 16);
+    }
+  }
+  static __device__ __forceinline__ bf16x8_t frag(const Raw& r, int s, int) {
+    const u32x4 wv = r.w[s >> 1];
+    return (s & 1) ? w8_frag(wv[2], wv[3]) : w8_frag(wv[0], wv[1]);
+  }
+  __device__ __forceinline__ f32x4 out_scale(int n) const { return *reinterpret_cast<const f32x4*>(s + n); }
+};
+
 // y[m][n..n+3] = bf16((part[0] + part[1] + ... in range order) * s[n])
 __global__ __launch_bounds__(256) void linear_w8_combine_kernel(const float* __restrict__ part, const float* __restrict__ s,
                                                                 bf16_t* __restrict__ y, long long ldy, int M, int N,
@@ -207,6 +230,19 @@ int w8_splits(int N, int K) {
 
 bool w8_shape_ok(int N, int K) { return N > 0 && K > 0 && N % 16 == 0 && K % 128 == 0; }
 
+// the argument checks of both linear entries (0: take the call) and the K ranges: `per` 128-deep blocks in each
+// of `splits`
+int w8_check(const void* x, const void* wq, const void* scale, const void* y, const void* ws, long long ws_bytes, int M,
+             int N, int K, long long ldx, long long ldy, int& splits, int& per) {
+  if (!w8_shape_ok(N, K) || M < 1 || (M + 31) / 32 > 65535) return -1;
+  if ((ldx | ldy) & 7 || ldx < K || ldy < N) return -2;
+  if (((uintptr_t)x | (uintptr_t)wq | (uintptr_t)scale | (uintptr_t)y) & 15) return -2;
+  splits = w8_splits(N, K);
+  per = (K / 128 + splits - 1) / splits;
+  if (splits > 1 && (!ws || ((uintptr_t)ws & 15) || ws_bytes < (long long)splits * M * N * 4)) return -3;
+  return 0;
+}
+
 }  // namespace
 
 // K ranges rca_linear_w8a16 uses for an [N][K] weight (a function of N and K only); 0: outside the contract
@@ -217,11 +253,8 @@ RCA_API int rca_linear_w8_splits(int N, int K) { return w8_shape_ok(N, K) ? w8_s
 // -1: shape outside the contract (K % 128, N % 16, M >= 1); -2: alignment / stride; -3: workspace.
 RCA_API int rca_linear_w8a16(const void* x, const void* wq, const void* scale, void* y, void* ws, long long ws_bytes,
                              int M, int N, int K, long long ldx, long long ldy, hipStream_t st) {
-  if (!w8_shape_ok(N, K) || M < 1 || (M + 31) / 32 > 65535) return -1;
-  if ((ldx | ldy) & 7 || ldx < K || ldy < N) return -2;
-  if (((uintptr_t)x | (uintptr_t)wq | (uintptr_t)scale | (uintptr_t)y) & 15) return -2;
-  const int splits = w8_splits(N, K), kblocks = K / 128, per = (kblocks + splits - 1) / splits;
-  if (splits > 1 && (!ws || ((uintptr_t)ws & 15) || ws_bytes < (long long)splits * M * N * 4)) return -3;
+  int splits, per;
+  if (const int rc = w8_check(x, wq, scale, y, ws, ws_bytes, M, N, K, ldx, ldy, splits, per)) return rc;
   const bool one = M <= 16;
   const dim3 grid((N + kBN - 1) / kBN, one ? 1 : (M + 31) / 32, splits);
   const bf16_t* xp = (const bf16_t*)x;
@@ -240,6 +273,23 @@ RCA_API int rca_linear_w8a16(const void* x, const void* wq, const void* scale, v
     linear_w8a16_kernel<1, false><<<grid, 256, 0, st>>>(xp, ldx, wp, sp, yp, ldy, pp, M, N, K, per);
   } else {
     linear_w8a16_kernel<2, false><<<grid, 256, 0, st>>>(xp, ldx, wp, sp, yp, ldy, pp, M, N, K, per);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// rca_linear_w8a16 for the rows above its tile (arguments, return codes and workspace rule are its own; any
+// M >= 1 is taken): the weight is streamed and converted once per 128 rows of x (linear_mid.h). Bit for bit
+// rca_linear_w8a16's output.
+RCA_API int rca_linear_w8a16_mid(const void* x, const void* wq, const void* scale, void* y, void* ws,
+                                 long long ws_bytes, int M, int N, int K, long long ldx, long long ldy, hipStream_t st) {
+  int splits, per;
+  if (const int rc = w8_check(x, wq, scale, y, ws, ws_bytes, M, N, K, ldx, ldy, splits, per)) return rc;
+  const W8Producer p{(const fp8_t*)wq, (const float*)scale};
+  if (!linear_mid_launch((const bf16_t*)x, ldx, p, (bf16_t*)y, ldy, (float*)ws, M, N, K, splits, per, st)) return -4;
+  if (splits > 1) {
+    const long long quads = (long long)M * (N / 4);
+    linear_w8_combine_kernel<<<(unsigned)((quads + 255) / 256), 256, 0, st>>>((float*)ws, p.s, (bf16_t*)y, ldy, M, N,
+                                                                             splits);
   }
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -12,8 +12,16 @@ model in the same run, at batch 1 and 32.
 ``--format mxfp4`` adds a third arm to both: ``ops._linear_w4_kernel`` on the MXFP4 quantisation of the
 same weight (its own bytes: N * K / 2 nibbles + N * K / 32 scales) and a model quantised to MXFP4.
 
+``--mid`` (how ``ops.M_MID`` / ``ops.M_MID_W4`` are set): per format and llama3-8b shape, for M in
+{33, 48, 64, 96, 128, 192, 256, 384, 512, 1024}, four arms interleaved round by round: ``kernel="mid"``,
+``kernel="dequant"`` (dequantise + ``F.linear``, what a quantised model runs above the thresholds),
+``kernel="skinny"``, and bf16 ``F.linear`` on a resident bf16 weight for context. Medians (us) with min and
+max, the mid arm's TB/s of its own weight bytes and TF/s, and per format the largest M of the grid up to
+which the mid arm is no slower than the dequant arm on every shape (a tie within the arms' spread goes
+to the mid arm).
+
     python scripts/linear_w8_bench.py [--rounds 10] [--models llama3-8b,llama3-1b] [--no-e2e] [--json out.json]
-                                      [--format mxfp4] [--ms 1,16,32,64] [--graph-decode]
+                                      [--format mxfp4] [--ms 1,16,32,64] [--graph-decode] [--mid]
 """
 import argparse
 import gc
@@ -33,6 +41,7 @@ from ray_community_amd.models import LLAMA_PRESETS, PagedKVCache, build_llama, w
 from ray_community_amd.ops import reference as ref  # noqa: E402
 
 MS = [1, 2, 4, 8, 16, 32, 64, 128]
+MID_MS = [33, 48, 64, 96, 128, 192, 256, 384, 512, 1024]
 
 
 def _time(fn, iters):
@@ -108,6 +117,46 @@ def kernel_bench(name, rounds, iters, ms, mxfp4):
     return rows
 
 
+def mid_bench(name, rounds, iters, ms):
+    rows, chosen = [], {}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for fmt in ("mxfp4", "fp8"):
+        ok = {M: True for M in ms}
+        for label, N, K in shapes(name):
+            w = torch.randn(N, K, device="cuda", generator=g) * 0.02
+            if fmt == "mxfp4":
+                linear, (q, s), wbytes = ops.linear_w4, ref.quantize_weight_mxfp4_ref(w), N * K // 2 + N * K // 32
+                wd = ops.dequant_w4(q, s)
+            else:
+                linear, (q, s), wbytes = ops.linear_w8, ref.quantize_weight_fp8_ref(w), N * K
+                wd = ops.dequant_w8(q, s)
+            del w
+            for M in ms:
+                x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16, generator=g)
+                out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+                arms = {a: (lambda a=a: linear(x, q, s, out=out, kernel=a)) for a in ("mid", "dequant", "skinny")}
+                arms["bf16"] = lambda: F.linear(x, wd)
+                same = torch.equal(arms["mid"]().clone(), arms["skinny"]())
+                for fn in arms.values():
+                    _time(fn, iters)
+                t = {a: [] for a in arms}
+                for _ in range(rounds):  # the timed rounds: every arm in every round
+                    for a, fn in arms.items():
+                        t[a].append(_time(fn, iters))
+                med = {a: statistics.median(v) for a, v in t.items()}
+                spread = max((max(v) - min(v)) / med[a] for a, v in t.items() if a in ("mid", "dequant"))
+                ok[M] &= med["mid"] <= med["dequant"] * (1 + spread)
+                rows.append(dict(format=fmt, linear=label, N=N, K=K, M=M, **{f"{a}_us": round(med[a], 2) for a in arms},
+                                 **{f"{a}_min_max": [round(min(v), 2), round(max(v), 2)] for a, v in t.items()},
+                                 spread=round(spread, 3), mid_weight_TBps=round(wbytes / med["mid"] * 1e-6, 3),
+                                 mid_TFps=round(2.0 * M * N * K / med["mid"] * 1e-6, 1), mid_equals_skinny=same))
+                print(json.dumps(rows[-1]), flush=True)
+            del q, s, wd
+        chosen[fmt] = max([m for i, m in enumerate(ms) if all(ok[v] for v in ms[:i + 1])], default=None)
+        print(json.dumps({"format": fmt, "mid_no_slower_on_every_shape": ok, "largest_M": chosen[fmt]}), flush=True)
+    return rows, chosen
+
+
 def e2e_bench(name, batches, new_tokens, prompt_len, reps, mxfp4=False, graph_decode=False):
     torch.manual_seed(0)
     model = build_llama(name, device="cuda").eval()
@@ -173,12 +222,16 @@ def main():
     ap.add_argument("--ms", default=",".join(map(str, MS)))
     ap.add_argument("--batches", default="1,32")
     ap.add_argument("--graph-decode", action="store_true", help="generate(graph_decode=True) in every arm")
+    ap.add_argument("--mid", action="store_true", help="the mid-M arms on llama3-8b's shapes instead of the kernel table")
     args = ap.parse_args()
     mxfp4 = args.format == "mxfp4"
     result = {"device": torch.cuda.get_device_name(0), "M_SKINNY": ops.M_SKINNY, "M_SKINNY_W4": ops.M_SKINNY_W4,
-              "kernel": [], "generate": []}
+              "M_MID": ops.M_MID, "M_MID_W4": ops.M_MID_W4, "kernel": [], "generate": []}
+    if args.mid:
+        ms = MID_MS if args.ms == ",".join(map(str, MS)) else [int(m) for m in args.ms.split(",")]
+        result["mid"], result["mid_largest_M"] = mid_bench("llama3-8b", args.rounds, args.iters, ms)
     for name in args.models.split(","):
-        if not args.no_kernel:
+        if not args.no_kernel and not args.mid:
             result["kernel"] += kernel_bench(name, args.rounds, args.iters, [int(m) for m in args.ms.split(",")], mxfp4)
         if not args.no_e2e:
             result["generate"] += e2e_bench(name, [int(b) for b in args.batches.split(",")], args.new_tokens,
