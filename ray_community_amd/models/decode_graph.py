@@ -19,9 +19,19 @@ The first step at a width runs the body eagerly on a side stream (the library lo
 handles and workspaces and the RoPE table must exist before a capture; it is a real step), the
 second captures and replays. The captured region is one stream, a linear chain of kernels.
 
-A round the graph cannot serve runs ``Llama.decode_step`` and is counted in ``stats``: one in which
-a row names a LoRA adapter (the routing is built on the host per call). ``stats`` is ``{"graphs",
-"replays", "eager_warm", "eager_fallback"}``.
+A round in which a row names a LoRA adapter is a graph of its own per width. The runner resolves the
+names to slots on the host and writes them into a static int32 ``[batch]`` region of the same buffer;
+the body then builds the routing on the device (``ops.lora_routing`` on that region: one launch of
+``lora_align_kernel``, nothing read back, arrays of a capacity that depends on the batch size and the
+slot count only) and sets it as ``LoraBank.routing`` while the layers run, so every ``LoraLinear``
+launches ``ops.lora_add_`` over that capacity and the tiles the round does not use return at once. A
+round without adapters replays the plain graph: its launches are what they were. ``load_adapter`` and
+``unload_adapter`` write the banks in place, so the graphs see the new bytes.
+
+A round the graph cannot serve runs ``Llama.decode_step`` and is counted in ``stats``: a LoRA round
+on a model that is not on a GPU, or one of whose ``LoraLinear``s ``ops.lora_supported`` refuses.
+``stats`` is ``{"graphs", "replays", "eager_warm", "eager_fallback"}``; LoRA rounds count as warm,
+graph and replay like any other.
 
 A captured graph holds the addresses of the modules' tensors. ``Llama.module_epoch`` changes when a
 module is swapped (``quantize_weights_``, ``enable_lora_``) or the parameters move; the runner then
@@ -56,22 +66,27 @@ class DecodeRunner:
         self.stats = new_stats()
         cfg, page, B = model.cfg, cache.page_size, self.batch
         self.max_width = -(-cfg.max_seq_len // page)
-        # one int32 buffer: tokens (as int64) | context_lens | block_table (the widest bucket; a
-        # narrower one is a [B, W] view of the same words), so a step's inputs go up in one copy
-        self._table_at = 3 * B
+        # one int32 buffer: tokens (as int64) | context_lens | adapter slots | block_table (the widest
+        # bucket; a narrower one is a [B, W] view of the same words), so a step's inputs go up in one copy
+        self._table_at = 4 * B
         words = self._table_at + B * self.max_width
         self._dev = torch.zeros(words, dtype=torch.int32, device=self.device)
         self._host = torch.zeros(words, dtype=torch.int32, pin_memory=w.is_cuda)
         self.tokens = self._dev[: 2 * B].view(torch.int64)
         self.context_lens = self._dev[2 * B: 3 * B]
+        self.adapter_slots = self._dev[3 * B: 4 * B]  # -1: no adapter; read by the LoRA graphs only
         self._np = self._host.numpy()
         self._tokens_h = self._np[: 2 * B].view("int64")
         self._lens_h = self._np[2 * B: 3 * B]
+        self._slots_h = self._np[3 * B: 4 * B]
+        self._slots_h[:] = -1
         self.logits = torch.zeros(B, cfg.vocab_size, dtype=w.dtype, device=self.device)
         self._uploaded = torch.cuda.Event() if w.is_cuda else None
         self._pool = None
-        self._graphs, self._warm = {}, set()
+        self._graphs, self._warm = {}, set()            # plain rounds, by width
+        self._lora_graphs, self._lora_warm = {}, set()  # rounds with an adapter, by width
         self._epoch = model.module_epoch
+        self._lora_ok = None  # whether LoRA rounds run the body: decided once per module epoch
 
     # ---------------------------------------------------------------------------------- buffers
     def block_table(self, width: int):
@@ -93,12 +108,13 @@ class DecodeRunner:
             w = self.width_for(w + 1)
         return out
 
-    def _upload(self, width, tokens, seq_ids):
+    def _upload(self, width, tokens, seq_ids, slots=None):
         B = self.batch
         if self._uploaded is not None:
             self._uploaded.synchronize()  # the last copy out of the staging buffer is over
         table = self._np[self._table_at: self._table_at + B * width].reshape(B, width)
         self.cache.fill_decode_inputs(seq_ids, self._lens_h, table)
+        self._slots_h[:] = -1 if slots is None else slots
         on_device = torch.is_tensor(tokens) and tokens.device.type != "cpu"
         if not on_device:
             self._tokens_h[:] = tokens.tolist() if torch.is_tensor(tokens) else [int(t) for t in tokens]
@@ -110,9 +126,17 @@ class DecodeRunner:
             self.tokens.copy_(tokens.reshape(-1))
 
     # ------------------------------------------------------------------------------------- body
-    def _body(self, width):
-        """Embedding, the layers and the logits, reading the static buffers only."""
+    def _body(self, width, lora=False):
+        """Embedding, the layers and the logits, reading the static buffers only. ``lora``: group
+        ``adapter_slots`` on the device first and route the layers' ``LoraLinear``s by it."""
         model, cache = self.model, self.cache
+        if lora:
+            bank = model.lora
+            bank.routing = ops.lora_routing(self.adapter_slots, slots=bank.max_adapters)
+            try:
+                return self._body(width)
+            finally:
+                bank.routing = None
         cfg = model.cfg
         D, Hq, Hk = cfg.head_dim, cfg.num_heads, cfg.num_kv_heads
         cs = model.rope_table(self.device)
@@ -127,19 +151,20 @@ class DecodeRunner:
 
         self.logits.copy_(model.logits(model._run_layers(model.embed(self.tokens), attn)))
 
-    def _run(self, width, replay=True):
+    def _run(self, width, replay=True, lora=False):
         if not self.capture:
-            self._body(width)
+            self._body(width, lora)
             return
-        graph = self._graphs.get(width)
-        if graph is None and width not in self._warm:
+        graphs, warm = (self._lora_graphs, self._lora_warm) if lora else (self._graphs, self._warm)
+        graph = graphs.get(width)
+        if graph is None and width not in warm:
             cur = torch.cuda.current_stream(self.device)
             side = torch.cuda.Stream(self.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                self._body(width)
+                self._body(width, lora)
             cur.wait_stream(side)
-            self._warm.add(width)
+            warm.add(width)
             self.stats["eager_warm"] += 1
             return
         if graph is None:
@@ -147,8 +172,8 @@ class DecodeRunner:
                 self._pool = torch.cuda.graph_pool_handle()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, pool=self._pool):
-                self._body(width)
-            self._graphs[width] = graph
+                self._body(width, lora)
+            graphs[width] = graph
             self.stats["graphs"] += 1
         if replay:  # a capture records the step without running it
             graph.replay()
@@ -156,29 +181,51 @@ class DecodeRunner:
 
     def _check_epoch(self):
         if self._epoch != self.model.module_epoch:
-            self._graphs.clear()
-            self._warm.clear()
+            for held in (self._graphs, self._warm, self._lora_graphs, self._lora_warm):
+                held.clear()
             self._epoch = self.model.module_epoch
+            self._lora_ok = None
+
+    def _lora_rounds_run_the_body(self) -> bool:
+        """Whether a round with adapters runs the body: a LoRA model on a GPU, every ``LoraLinear``
+        of which passes ``ops.lora_supported`` at the runner's batch size."""
+        if self._lora_ok is None:
+            from .lora import LoraLinear
+
+            bank = getattr(self.model, "lora", None)
+            self._lora_ok = (bank is not None and self.device.type == "cuda" and bank.max_adapters <= 1024
+                             and all(ops.lora_supported(self.batch, m.out_features, m.in_features, m.lora_A.shape[1],
+                                                        m.lora_A, m.lora_B, m.lora_scale)
+                                     for m in self.model.modules() if isinstance(m, LoraLinear)))
+        return self._lora_ok
 
     # ----------------------------------------------------------------------------------- public
     @torch.inference_mode()
     def step(self, tokens, seq_ids, *, adapters=None):
         """One new token per sequence, as ``Llama.decode_step``: the ``max_seq_len`` check, all or
         nothing allocation (``KVCacheFull`` leaves the cache as it was), then the body. With an
-        adapter named in ``adapters`` the round runs ``decode_step`` itself."""
+        adapter named in ``adapters`` the round runs the LoRA body (its own graph per width) where
+        the model is on a GPU and the LoRA kernels take its shapes, and ``decode_step`` otherwise."""
         model, cache, B = self.model, self.cache, self.batch
         if len(tokens) != B or len(seq_ids) != B or (adapters is not None and len(adapters) != B):
             raise ValueError(f"tokens, seq_ids and adapters must have the runner's batch size {B}")
-        if adapters is not None and any(a is not None for a in adapters):
-            self.stats["eager_fallback"] += 1
-            return model.decode_step(tokens, cache, seq_ids, adapters=adapters)
         self._check_epoch()
+        slots = None
+        if adapters is not None and any(a is not None for a in adapters):
+            if not self._lora_rounds_run_the_body():
+                self.stats["eager_fallback"] += 1
+                return model.decode_step(tokens, cache, seq_ids, adapters=adapters)
+            known = model.lora.slots
+            unknown = {a for a in adapters if a is not None and a not in known}
+            if unknown:
+                raise ValueError(f"unknown adapter(s) {sorted(map(str, unknown))}: loaded are {sorted(known)}")
+            slots = [-1 if a is None else known[a] for a in adapters]
         if max(cache.length(s) if s is not None else 0 for s in seq_ids) >= model.cfg.max_seq_len:
             raise ValueError(f"sequence would exceed max_seq_len {model.cfg.max_seq_len}")
         model._allocate(cache, [(s, 1) for s in seq_ids])
         width = self.width_for(max(cache.blocks_held(s) if s is not None else 0 for s in seq_ids))
-        self._upload(width, tokens, seq_ids)
-        self._run(width)
+        self._upload(width, tokens, seq_ids, slots)
+        self._run(width, lora=slots is not None)
         return self.logits
 
     def count_fallback(self):
@@ -188,16 +235,20 @@ class DecodeRunner:
     @torch.inference_mode()
     def warmup(self):
         """Capture every bucket now, for servers that want no capture latency in flight. Runs the
-        body with every row inactive (context length 0), which writes nothing to the cache."""
+        body with every row inactive (context length 0), which writes nothing to the cache. Where
+        LoRA rounds run the body their graphs are captured too, with no row naming an adapter."""
         self._check_epoch()
         if not self.capture:
             return self
         self._dev.zero_()
-        for width in self.widths():
-            if width not in self._graphs:
-                if width not in self._warm:
-                    self._run(width)
-                self._run(width, replay=False)
+        self.adapter_slots.fill_(-1)
+        for lora in (False, True) if self._lora_rounds_run_the_body() else (False,):
+            graphs, warm = (self._lora_graphs, self._lora_warm) if lora else (self._graphs, self._warm)
+            for width in self.widths():
+                if width not in graphs:
+                    if width not in warm:
+                        self._run(width, lora=lora)
+                    self._run(width, replay=False, lora=lora)
         torch.cuda.current_stream(self.device).synchronize()
         return self
 

@@ -216,8 +216,9 @@ def decode_round(model, cache, slots, proposer, num_draft, stats, sample=sample_
 
     ``runner`` (a ``models.decode_graph.DecodeRunner`` over ``model``, ``cache`` and ``len(slots)``
     rows; ``graph_decode=True`` of the callers): its ``step`` takes the place of ``decode_step``. It
-    runs a LoRA round through ``decode_step`` itself, and a verify round goes through ``extend`` as
-    ever; the runner counts both as eager fallbacks."""
+    replays a LoRA round as a graph of its own on a GPU and runs it through ``decode_step`` itself
+    elsewhere, and a verify round goes through ``extend`` as ever; the runner counts the latter two
+    as eager fallbacks."""
     live = [s for s, st in enumerate(slots) if st is not None]
     if not live:
         return []

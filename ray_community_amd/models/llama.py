@@ -536,7 +536,8 @@ class Llama(nn.Module):
         ``graph_decode=True`` runs the decode steps through a ``DecodeRunner``
         (``models/decode_graph.py``): static input buffers and one captured HIP graph per block-table
         bucket, replayed per step; the same body uncaptured when the model is not on a GPU. LoRA
-        rounds and speculative verify rounds run as without it. A runner belongs to a cache, so pass
+        rounds replay a graph of their own on a GPU (the routing is built on the device); on a CPU
+        model they run as without it, as speculative verify rounds do. A runner belongs to a cache, so pass
         ``cache=`` to keep its graphs from one call to the next."""
         from .decoding import Sampling, Stream, _seeded_generator, decode_round, sample_rows, sample_tokens
         from .kv_cache import PagedKVCache

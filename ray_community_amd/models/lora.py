@@ -7,8 +7,10 @@ weights, selected per request.
 block in ``LoraLinear``: the base module (plain or ``QuantLinear``) untouched, plus that target's bank
 of ``max_adapters`` slots (``A [S, R, in]``, ``B [S, out, R]``, ``scale [S]`` fp32). A forward call names
 an adapter (or ``None``) per row; ``LoraLinear`` runs the base and then ``ops.lora_add_`` on its result
-(``ops/csrc/lora.hip``: two launches per target, whatever the number of adapters in the batch). Without
-a named adapter nothing is launched and every logit keeps its bits.
+(``ops/csrc/lora.hip``: two launches per target, or one up to ``ops.M_LORA_FUSED`` rows, whatever the
+number of adapters in the batch). Without a named adapter nothing is launched and every logit keeps its
+bits. ``LoraBank.routing`` is set by ``LoraBank.route`` (names, grouped on the host) or by
+``DecodeRunner`` (slots in a static device buffer, grouped on the device inside a captured graph).
 """
 from __future__ import annotations
 

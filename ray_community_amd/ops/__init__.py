@@ -1900,7 +1900,8 @@ class LoraRouting:
     """Which adapter slot each row of one forward call takes (``lora_routing``). ``idx [M]`` int32 is
     the slot per row (-1: none); ``tile_slot [n_tiles]`` and ``tile_rows [n_tiles, 16]`` (-1: padding)
     group the rows with a slot into tiles of up to 16 rows of one slot; ``any`` is false when every
-    row is a base row. The three arrays are views of one device tensor: one upload per call."""
+    row is a base row. Built on the host, the three arrays are views of one tensor (one upload per
+    call); built on the device, ``n_tiles`` is the capacity and the unused tiles hold ``-1``."""
     __slots__ = ("idx", "tile_slot", "tile_rows", "n_tiles", "any", "num_rows")
 
     def __init__(self, idx, tile_slot, tile_rows):
@@ -1909,10 +1910,32 @@ class LoraRouting:
         self.any = self.n_tiles > 0
 
 
-def lora_routing(adapters, device=None):
+def lora_routing(adapters, device=None, *, slots=None):
     """The routing of a batch whose row ``m`` takes adapter slot ``adapters[m]`` (``-1`` or ``None``:
     no adapter). Slots are taken in ascending order, the rows of a slot in ascending order, 16 to a
-    tile; the rows of a slot need not be contiguous. Built on the host and uploaded once."""
+    tile; the rows of a slot need not be contiguous.
+
+    A list is grouped on the host and uploaded once. A CUDA int32 tensor ``[M]`` with ``slots`` (the
+    bank's slot count ``S``, at most 1024) is grouped by one launch of ``lora_align_kernel`` and
+    nothing is read back, so the call can be captured in a graph: the arrays have the capacity
+    ``min(M, min(S, M) + M // 16)``, the tiles in use come first and in the host's order, the rest is ``-1``
+    (the kernels return at such a tile); ``n_tiles`` is that capacity and ``any`` is true whatever
+    the rows name. A value outside ``[0, S)`` names no adapter. A tensor that is not on a GPU is
+    refused with ``ValueError``: grouping it here would read it, which is what the list path is for."""
+    if torch.is_tensor(adapters):
+        if not (adapters.is_cuda and adapters.dtype == torch.int32 and adapters.dim() == 1 and adapters.is_contiguous()):
+            raise ValueError("lora_routing: a tensor of slots must be a contiguous CUDA int32 [M] tensor "
+                             "(pass a list to group on the host)")
+        M, S = int(adapters.shape[0]), 0 if slots is None else int(slots)
+        L = lib()
+        n = L.rca_lora_tiles_max(M, S)
+        if n == 0:
+            raise ValueError(f"lora_routing: M = {M} rows >= 1 and 1 <= slots <= 1024 are needed, got slots={slots}")
+        flat = torch.empty(n * (1 + LORA_TILE), dtype=torch.int32, device=adapters.device)
+        routing = LoraRouting(adapters, flat[:n], flat[n:].view(n, LORA_TILE))
+        check(L.rca_lora_align(adapters.data_ptr(), routing.tile_slot.data_ptr(), routing.tile_rows.data_ptr(), M, S, n,
+                               stream_ptr(adapters.device)), "lora_align")
+        return routing
     idx = [-1 if a is None else int(a) for a in adapters]
     if any(a < -1 for a in idx):
         raise ValueError("lora_routing: a slot is >= 0, or -1 / None for no adapter")
@@ -1955,7 +1978,7 @@ def lora_supported(M: int, N: int, K: int, R: int, *tensors) -> bool:
 
 
 def _lora_kernel(y, x, A, B, scale, routing):
-    """The two launches on operands ``lora_supported`` accepts."""
+    """The two launches (shrink, expand-add) on operands ``lora_supported`` accepts."""
     (M, N), K = y.shape, x.shape[1]
     S, R = A.shape[0], A.shape[1]
     L = lib()
@@ -1967,7 +1990,26 @@ def _lora_kernel(y, x, A, B, scale, routing):
     return y
 
 
-def lora_add_(y, x, A, B, scale, routing):
+def _lora_fused_kernel(y, x, A, B, scale, routing, nb=0):
+    """One launch, no workspace, on operands ``lora_supported`` accepts with ``R <= _LORA_FUSED_MAX_R``."""
+    (M, N), K = y.shape, x.shape[1]
+    S, R = A.shape[0], A.shape[1]
+    check(lib().rca_lora_add_fused(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), A.data_ptr(), B.data_ptr(),
+                                   scale.data_ptr(), routing.tile_slot.data_ptr(), routing.tile_rows.data_ptr(),
+                                   routing.n_tiles, nb, M, N, K, R, S, stream_ptr(y.device)), "lora_add_fused")
+    return y
+
+
+# Rows up to which ``lora_add_(kernel="auto")`` takes the fused kernel (one launch per target, the shrink
+# recomputed by every block of output columns) instead of the two-pass kernels; the arms are bitwise equal,
+# so this moves time only. The largest measured M up to which the fused kernel wins on every llama3-8b layer
+# shape under a graph (profiles/lora_graph.md): at M = 1 it wins on ``o`` alone and loses on the other three,
+# so it is 0 and the fused kernel is opt-in (``kernel="fused"``).
+M_LORA_FUSED = 0
+_LORA_FUSED_MAX_R = 128  # the fused kernel keeps every range's fp32 partials in LDS: 64 KB at this capacity
+
+
+def lora_add_(y, x, A, B, scale, routing, kernel="auto"):
     """Add each row's LoRA update to the base output ``y [M, N]`` of a linear with input ``x [M, K]``,
     in place; returns ``y``. ``A [S, R, K]``, ``B [S, N, R]`` and ``scale [S]`` (fp32) are the stacked
     adapters of ``S`` slots of capacity ``R``; ``routing`` (``lora_routing``) names the slot of every
@@ -1975,11 +2017,18 @@ def lora_add_(y, x, A, B, scale, routing):
     bf16 once, ``y + scale * B t`` accumulated in fp32 and rounded once; rows without an adapter keep
     their bits. No autograd: inference only.
 
-    bf16 CUDA operands within ``lora_supported`` run the two gfx950 kernels of ``ops/csrc/lora.hip``
-    (an output row depends on its own input row and its slot only, bitwise, whatever the batch is); an
+    bf16 CUDA operands within ``lora_supported`` run the gfx950 kernels of ``ops/csrc/lora.hip`` (an
+    output row depends on its own input row and its slot only, bitwise, whatever the batch is); an
     ``x`` with a non-unit inner stride or a misaligned base is made contiguous first. CPU tensors,
     other dtypes and shapes outside the contract run the reference. With ``routing.any`` false nothing
-    is launched."""
+    is launched.
+
+    ``kernel``: ``"two_pass"`` is shrink then expand-add through an fp32 workspace, ``"fused"`` one
+    launch without a workspace (``R <= 128``); they give the same bits, so ``"auto"`` (fused up to
+    ``M_LORA_FUSED`` rows) changes no result. A forced arm never falls back: it raises ``ValueError``
+    where the reference would run or, for ``"fused"``, where ``R`` is above 128."""
+    if kernel not in ("auto", "two_pass", "fused"):
+        raise ValueError(f"lora_add_: kernel must be 'auto', 'two_pass' or 'fused', got {kernel!r}")
     if y.dim() != 2 or x.dim() != 2 or A.dim() != 3 or B.dim() != 3:
         raise ValueError("lora_add_: y [M, N], x [M, K], A [S, R, K] and B [S, N, R] are expected")
     (M, N), K = y.shape, x.shape[1]
@@ -1992,9 +2041,15 @@ def lora_add_(y, x, A, B, scale, routing):
         return y
     if x.is_cuda and x.dtype == torch.bfloat16 and not _lora_tensor_ok(x):
         x = x.contiguous()
-    if lora_supported(M, N, K, R, y, x, A, B, scale) and routing.idx.device == y.device:
-        return _lora_kernel(y, x, A, B, scale, routing)
-    return ref.lora_add_ref(y, x, A, B, scale, routing.idx)
+    hip = lora_supported(M, N, K, R, y, x, A, B, scale) and routing.idx.device == y.device
+    if kernel != "auto" and not (hip and (kernel == "two_pass" or R <= _LORA_FUSED_MAX_R)):
+        raise ValueError(f"lora_add_: kernel={kernel!r} does not take these operands (lora_supported"
+                         f"{', R <= 128' if kernel == 'fused' else ''}): M={M} N={N} K={K} R={R}")
+    if not hip:
+        return ref.lora_add_ref(y, x, A, B, scale, routing.idx)
+    if kernel == "fused" or (kernel == "auto" and R <= _LORA_FUSED_MAX_R and M <= M_LORA_FUSED):
+        return _lora_fused_kernel(y, x, A, B, scale, routing)
+    return _lora_kernel(y, x, A, B, scale, routing)
 
 
 # ----------------------------------------------------------------------------------- mixture of experts

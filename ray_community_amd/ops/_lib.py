@@ -112,6 +112,9 @@ _SIGS = {
     "rca_lora_splits": (c_int, [c_int, c_int]),
     "rca_lora_add": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_int, c_void_p, c_ll] + [c_int] * 5
                      + [c_void_p]),
+    "rca_lora_tiles_max": (c_int, [c_int, c_int]),
+    "rca_lora_align": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    "rca_lora_add_fused": (c_int, [c_void_p, c_ll, c_void_p, c_ll] + [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     "rca_moe_down_splits": (c_int, [c_int, c_int]),
     "rca_moe_ffn_workspace": (c_ll, [c_int] * 5),
     "rca_moe_route": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),

@@ -23,6 +23,22 @@
 // whatever M is and in whichever tile and position the row sits (an MFMA column depends on its own column
 // operand only), and results are bitwise reproducible. Padding rows of a tile are zeros in LDS and are
 // not stored.
+//
+// Routing on the device. lora_align_kernel (one workgroup, in the manner of moe_align_kernel) turns idx [M]
+// into the same two arrays in the host's order (slots ascending, the rows of a slot ascending, 16 to a tile),
+// sized n_tiles_max = min(M, min(S, M) + M / 16) -- a function of M and S only, so a captured grid never
+// changes -- with -1 past the tiles in use. Every kernel here returns at a tile whose slot is -1.
+//
+// One launch. lora_fused_kernel<RT> (R = 16 RT <= 128): grid (n_tiles_max, NB), 8 waves. Every block
+// recomputes its tile's shrink: wave w owns the K ranges w, w + 8, ... of lora_splits(K, R), and per
+// 128-deep chunk loads its lane's 64 bytes of x (the column operand, straight from global: no other wave
+// reads that range, so LDS staging would share nothing) and of each of the RT row tiles of A[slot], then
+// RT x 4 MFMAs in the two-pass order. The fp32 partials [splits][16][R] go to LDS (at most 64 KB), are added
+// in ascending range order and rounded to bf16 once into the t tile, which overlays the partials (each
+// thread holds its sums in registers across the barrier). All 8 waves then expand over the block's share of
+// the 16-column tiles with expand_add_tile, the function lora_expand_add_kernel runs. Ranges, chunk order,
+// range order, r0 chain and epilogue are the two-pass kernels': the result equals theirs bit for bit,
+// whatever NB is. NB trades occupancy against NB reads of A[slot] from L2; a block waits for no other.
 #include "common.h"
 
 namespace {
@@ -137,6 +153,35 @@ __global__ __launch_bounds__(64 * NW) void lora_shrink_kernel(const bf16_t* __re
   }
 }
 
+// One wave, one 16-column tile at n0: acc = B[slot][n0 .. n0 + 16][:] . t over R in 32-deep MFMAs (t: the
+// bf16 tile in LDS, rows of rowb bytes), then y[row][n0 + 4 g ..] = bf16(float(y) + sc * acc) for a real row.
+__device__ __forceinline__ void expand_add_tile(const bf16_t* __restrict__ B, const char* lds, int rowb,
+                                                bf16_t* __restrict__ y, long long ldy, int row, int M, int N, int R,
+                                                int slot, float sc, int n0, int ln, int g) {
+  const bf16_t* brow = B + ((size_t)slot * N + n0 + ln) * R + 8 * g;
+  const char* tb = lds + ln * rowb + g * 16;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int r0 = 0; r0 < R; r0 += 32) {
+    u32x4 bv = u32x4{0u, 0u, 0u, 0u}, tv = u32x4{0u, 0u, 0u, 0u};
+    if (r0 + 8 * g < R) {  // R % 32 == 16: the last MFMA's upper half is zeros
+      bv = *reinterpret_cast<const u32x4*>(brow + r0);
+      tv = *reinterpret_cast<const u32x4*>(tb + r0 * 2);
+    }
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, bv), __builtin_bit_cast(bf16x8_t, tv), acc,
+                                                  0, 0, 0);
+  }
+  // lane holds D[n = n0 + 4 g + i][m = ln]
+  if (row < 0 || row >= M) return;
+  uint2* yp = reinterpret_cast<uint2*>(y + (size_t)row * ldy + n0 + 4 * g);
+  const uint2 y0 = *yp;
+  uint2 o;
+  o.x = (unsigned)f2bf(bf2f((bf16_t)(y0.x & 0xffffu)) + sc * acc[0]) |
+        ((unsigned)f2bf(bf2f((bf16_t)(y0.x >> 16)) + sc * acc[1]) << 16);
+  o.y = (unsigned)f2bf(bf2f((bf16_t)(y0.y & 0xffffu)) + sc * acc[2]) |
+        ((unsigned)f2bf(bf2f((bf16_t)(y0.y >> 16)) + sc * acc[3]) << 16);
+  *yp = o;
+}
+
 __global__ __launch_bounds__(256) void lora_expand_add_kernel(const float* __restrict__ part, const bf16_t* __restrict__ B,
                                                               const float* __restrict__ scale,
                                                               const int* __restrict__ tile_slot,
@@ -171,31 +216,155 @@ __global__ __launch_bounds__(256) void lora_expand_add_kernel(const float* __res
 
   const int n0 = blockIdx.y * kBN + wave * 16;
   if (n0 >= N) return;  // N % 16 == 0: a wave has a whole tile or none
-  const bf16_t* brow = B + ((size_t)slot * N + n0 + ln) * R + 8 * g;
-  const char* tb = lds + ln * rowb + g * 16;
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int r0 = 0; r0 < R; r0 += 32) {
-    u32x4 bv = u32x4{0u, 0u, 0u, 0u}, tv = u32x4{0u, 0u, 0u, 0u};
-    if (r0 + 8 * g < R) {  // R % 32 == 16: the last MFMA's upper half is zeros
-      bv = *reinterpret_cast<const u32x4*>(brow + r0);
-      tv = *reinterpret_cast<const u32x4*>(tb + r0 * 2);
-    }
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, bv), __builtin_bit_cast(bf16x8_t, tv), acc,
-                                                  0, 0, 0);
-  }
-
-  // lane holds D[n = n0 + 4 g + i][m = ln]
   const int row = tile_rows[tile * kTileRows + ln];
-  if (row < 0 || row >= M) return;
+  expand_add_tile(B, lds, rowb, y, ldy, row, M, N, R, slot, scale[slot], n0, ln, g);
+}
+
+// ------------------------------------------------------------------------------------- one launch
+constexpr int kFusedWaves = 8;
+constexpr int kFusedMaxR = 128;       // splits * 16 * R * 4 bytes of partials: 64 KB at most
+constexpr int kFusedTargetBlocks = 64;
+
+// grid (n_tiles, NB); dynamic LDS: splits * 16 * R * 4 bytes (the t tile overlays it). tiles_per: 16-column
+// tiles per block.
+template <int RT>
+__global__ __launch_bounds__(64 * kFusedWaves) void lora_fused_kernel(
+    const bf16_t* __restrict__ x, long long ldx, const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
+    const float* __restrict__ scale, const int* __restrict__ tile_slot, const int* __restrict__ tile_rows,
+    bf16_t* __restrict__ y, long long ldy, int M, int N, int K, int S, int splits, int per, int tiles_per) {
+  constexpr int R = 16 * RT, kThreads = 64 * kFusedWaves, kQuads = R / 4;
+  constexpr int kRowB = R * 2 + 16;
+  static_assert(kTileRows * kQuads <= kThreads, "one quad of t per thread");
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  float* part = reinterpret_cast<float*>(lds);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ln = lane & 15, g = lane >> 4;
+  const int tile = blockIdx.x;
+  const int slot = tile_slot[tile];
+  if (slot < 0 || slot >= S) return;  // the whole block, before any barrier
+  const int row = tile_rows[tile * kTileRows + ln];
+  const bool real = row >= 0 && row < M;
+  const int kblocks = K / 128;
+
+  // shrink: lane (ln, g) holds x[row ln][k + 32 g ..] and A[16 rt + ln][k + 32 g ..], 64 bytes each a chunk
+  const bf16_t* xrow = x + (real ? (size_t)row * ldx : 0) + g * 32;
+  const bf16_t* arow = A + ((size_t)slot * R + ln) * K + g * 32;
+  for (int z = wave; z < splits; z += kFusedWaves) {
+    const int kb0 = min(z * per, kblocks), kb1 = min(kb0 + per, kblocks);
+    f32x4 acc[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k = kb0 * 128; k < kb1 * 128; k += 128) {
+      u32x4 xf[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        xf[j] = u32x4{0u, 0u, 0u, 0u};  // a padding row is zeros
+        if (real) xf[j] = *reinterpret_cast<const u32x4*>(xrow + k + 8 * j);
+      }
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        const bf16_t* ap = arow + (size_t)t * 16 * K + k;
+        bf16x8_t af[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) af[j] = *reinterpret_cast<const bf16x8_t*>(ap + 8 * j);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j], __builtin_bit_cast(bf16x8_t, xf[j]), acc[t], 0, 0, 0);
+      }
+    }
+    // lane holds D[r = 16 t + 4 g + i][m = ln]
+    float* prow = part + ((size_t)z * kTileRows + ln) * R + 4 * g;
+#pragma unroll
+    for (int t = 0; t < RT; ++t) *reinterpret_cast<f32x4*>(prow + t * 16) = acc[t];
+  }
+  lds_barrier();
+
+  // reduce: t[m][r..r+3] = bf16(part[0] + part[1] + ... in range order), written over the partials
+  const bool mine = tid < kTileRows * kQuads;
+  const int m = tid / kQuads, r = (tid % kQuads) * 4;
+  f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (mine) {
+    const float* p = part + (size_t)m * R + r;
+    a = *reinterpret_cast<const f32x4*>(p);
+    for (int z = 1; z < splits; ++z) {
+      const f32x4 b = *reinterpret_cast<const f32x4*>(p + (size_t)z * kTileRows * R);
+      a[0] += b[0], a[1] += b[1], a[2] += b[2], a[3] += b[3];
+    }
+  }
+  lds_barrier();  // every partial is in registers
+  if (mine) {
+    uint2 o;
+    o.x = (unsigned)f2bf(a[0]) | ((unsigned)f2bf(a[1]) << 16);
+    o.y = (unsigned)f2bf(a[2]) | ((unsigned)f2bf(a[3]) << 16);
+    *reinterpret_cast<uint2*>(lds + m * kRowB + r * 2) = o;
+  }
+  lds_barrier();
+
+  // expand: the block's 16-column tiles dealt to the waves
   const float sc = scale[slot];
-  uint2* yp = reinterpret_cast<uint2*>(y + (size_t)row * ldy + n0 + 4 * g);
-  const uint2 y0 = *yp;
-  uint2 o;
-  o.x = (unsigned)f2bf(bf2f((bf16_t)(y0.x & 0xffffu)) + sc * acc[0]) |
-        ((unsigned)f2bf(bf2f((bf16_t)(y0.x >> 16)) + sc * acc[1]) << 16);
-  o.y = (unsigned)f2bf(bf2f((bf16_t)(y0.y & 0xffffu)) + sc * acc[2]) |
-        ((unsigned)f2bf(bf2f((bf16_t)(y0.y >> 16)) + sc * acc[3]) << 16);
-  *yp = o;
+  for (int i = wave; i < tiles_per; i += kFusedWaves) {
+    const int n0 = ((int)blockIdx.y * tiles_per + i) * 16;
+    if (n0 >= N) break;
+    expand_add_tile(B, lds, kRowB, y, ldy, row, M, N, R, slot, sc, n0, ln, g);
+  }
+}
+
+// --------------------------------------------------------------------------------- routing on device
+constexpr int kAlignThreads = 1024;
+constexpr int kAlignMaxSlots = 1024;
+
+// wave w owns the slots w, w + 16, ...; a scan of idx takes 64 rows a step, in ascending row order
+__global__ __launch_bounds__(kAlignThreads) void lora_align_kernel(const int* __restrict__ idx, int* __restrict__ tile_slot,
+                                                                   int* __restrict__ tile_rows, int M, int S,
+                                                                   int n_tiles_max) {
+  constexpr int kWaves = kAlignThreads / 64;
+  __shared__ int count[kAlignMaxSlots], first[kAlignMaxSlots + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+
+  for (int s = wave; s < S; s += kWaves) {
+    int c = 0;
+    for (int m0 = 0; m0 < M; m0 += 64) {
+      const int m = m0 + lane;
+      c += __popcll(__ballot(m < M && idx[m] == s));
+    }
+    if (lane == 0) count[s] = c;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int at = 0;
+    for (int s = 0; s < S; ++s) {
+      first[s] = at;
+      at += (count[s] + kTileRows - 1) / kTileRows;
+    }
+    first[S] = at;  // <= n_tiles_max: at most min(S, M) partly filled tiles and M / 16 full ones, and <= M
+  }
+  __syncthreads();
+
+  for (int s = wave; s < S; s += kWaves) {
+    const int tiles = first[s + 1] - first[s];
+    if (tiles == 0) continue;
+    int* out = tile_rows + (size_t)first[s] * kTileRows;
+    int c = 0;
+    for (int m0 = 0; m0 < M; m0 += 64) {
+      const int m = m0 + lane;
+      const bool mine = m < M && idx[m] == s;
+      const unsigned long long b = __ballot(mine);
+      if (mine) out[c + __popcll(b & below)] = m;
+      c += __popcll(b);
+    }
+    for (int i = c + lane; i < tiles * kTileRows; i += 64) out[i] = -1;
+    for (int i = lane; i < tiles; i += 64) tile_slot[first[s] + i] = s;
+  }
+  const int used = first[S];
+  for (int i = used + tid; i < n_tiles_max; i += kAlignThreads) tile_slot[i] = -1;
+  for (int i = used * kTileRows + tid; i < n_tiles_max * kTileRows; i += kAlignThreads) tile_rows[i] = -1;
+}
+
+int lora_tiles_max(int M, int S) {
+  const int most = (S < M ? S : M) + M / kTileRows;
+  return most < M ? most : M;
 }
 
 int lora_splits(int K, int R) {
@@ -248,5 +417,61 @@ RCA_API int rca_lora_add(const void* x, long long ldx, void* y, long long ldy, c
   lora_expand_add_kernel<<<dim3(n_tiles, (N + kBN - 1) / kBN), 256, 0, st>>>(pp, (const bf16_t*)B, (const float*)scale, ts,
                                                                             tr, (bf16_t*)y, ldy, n_tiles, M, N, R, S,
                                                                             splits);
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// Tiles that the routing of M rows over S slots can need: min(M, min(S, M) + M / 16); 0: outside the contract
+RCA_API int rca_lora_tiles_max(int M, int S) {
+  return M >= 1 && M <= (1 << 26) && S >= 1 && S <= kAlignMaxSlots ? lora_tiles_max(M, S) : 0;
+}
+
+// The routing of idx [M] int32 (a slot per row; anything outside [0, S) names no adapter and is grouped
+// nowhere) built on the device, reading nothing back: tile_slot [n_tiles_max] and tile_rows [n_tiles_max][16]
+// in the host's order (slots ascending, the rows of a slot ascending, 16 to a tile), -1 past the tiles in
+// use. n_tiles_max must be rca_lora_tiles_max(M, S).
+// -1: M or S outside 1 .. 2^26 / 1 .. 1024, or n_tiles_max is not the capacity; -2: a null or misaligned
+// pointer; -4: launch. Nothing is launched on a refusal.
+RCA_API int rca_lora_align(const void* idx, void* tile_slot, void* tile_rows, int M, int S, int n_tiles_max,
+                           hipStream_t st) {
+  if (rca_lora_tiles_max(M, S) == 0 || n_tiles_max != lora_tiles_max(M, S)) return -1;
+  if (!idx || !tile_slot || !tile_rows || (((uintptr_t)idx | (uintptr_t)tile_slot | (uintptr_t)tile_rows) & 3)) return -2;
+  lora_align_kernel<<<1, kAlignThreads, 0, st>>>((const int*)idx, (int*)tile_slot, (int*)tile_rows, M, S, n_tiles_max);
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// rca_lora_add in one launch and without a workspace, bit for bit: operands as there. nb: blocks of output
+// columns per tile (it does not enter the numerics); 0: as many as bring the grid to about 64 blocks.
+// -1: shape outside rca_lora_add's contract, R > 128 or nb < 0; -2: alignment / stride; -4: launch. Nothing
+// is launched on a refusal, nor with n_tiles == 0 (returns 0).
+RCA_API int rca_lora_add_fused(const void* x, long long ldx, void* y, long long ldy, const void* A, const void* B,
+                               const void* scale, const void* tile_slot, const void* tile_rows, int n_tiles, int nb, int M,
+                               int N, int K, int R, int S, hipStream_t st) {
+  if (!lora_shape_ok(N, K, R) || R > kFusedMaxR || M < 1 || S < 1 || n_tiles < 0 || nb < 0) return -1;
+  if ((ldx | ldy) & 7 || ldx < K || ldy < N) return -2;
+  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)A | (uintptr_t)B) & 15) return -2;
+  if (((uintptr_t)scale | (uintptr_t)tile_slot | (uintptr_t)tile_rows) & 3) return -2;
+  if (!scale || !tile_slot || !tile_rows) return -2;
+  if (n_tiles == 0) return 0;
+  const int splits = lora_splits(K, R), kblocks = K / 128, per = (kblocks + splits - 1) / splits;
+  const int ntiles16 = N / 16;
+  if (nb == 0) nb = (kFusedTargetBlocks + n_tiles - 1) / n_tiles;
+  nb = nb < ntiles16 ? nb : ntiles16;
+  const int tiles_per = (ntiles16 + nb - 1) / nb;
+  nb = (ntiles16 + tiles_per - 1) / tiles_per;  // no block without a tile
+  if (nb > 65535) return -1;
+  const size_t lds = (size_t)splits * kTileRows * R * 4;  // <= 64 KB: 16 ranges only up to R = 64
+  const dim3 grid(n_tiles, nb);
+#define RCA_LORA_FUSED(RT)                                                                                             \
+  case RT:                                                                                                             \
+    lora_fused_kernel<RT><<<grid, 64 * kFusedWaves, lds, st>>>((const bf16_t*)x, ldx, (const bf16_t*)A,                \
+                                                               (const bf16_t*)B, (const float*)scale,                  \
+                                                               (const int*)tile_slot, (const int*)tile_rows,           \
+                                                               (bf16_t*)y, ldy, M, N, K, S, splits, per, tiles_per);   \
+    break;
+  switch (R / 16) {
+    RCA_LORA_FUSED(1) RCA_LORA_FUSED(2) RCA_LORA_FUSED(3) RCA_LORA_FUSED(4)
+    RCA_LORA_FUSED(5) RCA_LORA_FUSED(6) RCA_LORA_FUSED(7) RCA_LORA_FUSED(8)
+  }
+#undef RCA_LORA_FUSED
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -11,7 +11,14 @@ process, with bf16 and with fp8 weights. ``extra_us_per_step`` is (time of the a
 new tokens, so it carries the prompt's share of the difference too; ``launch_share`` is 8 launches x layers x
 launch_floor_us / 2 over that.
 
+``--graph`` measures the graphed decode path instead (profiles/lora_graph.md). Op: per 8B layer shape and M in
+{1, 8, 32, 64}, with all rows on one adapter and with every row on its own, ``ops.lora_add_`` with
+``kernel="fused"`` against ``kernel="two_pass"``, both on device-built routing and both replayed from a
+captured graph of 16 calls, in alternating windows. End to end: ``generate`` at batch 1 and 32 with every
+sequence on its own adapter, graphed (``graph_decode=True``) against eager, and against the graphed base.
+
     python scripts/lora_bench.py [--rounds 10] [--models llama3-8b,llama3-1b] [--no-e2e] [--json out.json]
+    python scripts/lora_bench.py --graph [--rounds 10] [--models ...] [--no-op] [--no-e2e] [--json out.json]
 """
 import argparse
 import json
@@ -136,6 +143,100 @@ def e2e_bench(name, batches, new_tokens, prompt_len, reps, floor_us):
     return rows
 
 
+GRAPH_MS = [1, 8, 32, 64]
+GRAPH_CALLS = 16  # lora_add_ calls per captured graph: a replay is long enough to time
+
+
+def _graphed(fn):
+    """``fn`` run GRAPH_CALLS times in one captured graph (after one eager run on a side stream); returns
+    the replay."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(GRAPH_CALLS):
+            fn()
+    return graph.replay
+
+
+def graph_op_bench(name, rounds, iters):
+    """Fused against two-pass, both on device routing and both replayed from a graph (us per call, the
+    median of ``rounds`` windows of ``iters`` replays, the arms' windows alternating); ``nb`` is the fused
+    grid's second dimension."""
+    cfg, rows = LLAMA_PRESETS[name], []
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for target, (K, N) in lora_mod.target_dims(cfg).items():
+        R = -(-len(lora_mod.PARTS[target]) * RANK // 16) * 16
+        for M in GRAPH_MS:
+            x, y, A, B, scale = _op_case(M, N, K, R, g)
+            row = dict(model=name, linear=target, N=N, K=K, R=R, M=M, splits=ops.lib().rca_lora_splits(K, R))
+            for pattern, idx in (("one", [0] * M), ("own", [m % SLOTS for m in range(M)])):
+                routing = ops.lora_routing(torch.tensor(idx, dtype=torch.int32, device="cuda"), slots=SLOTS)
+                want = ops.lora_add_(y.clone(), x, A, B, scale, routing, kernel="two_pass")
+                assert torch.equal(ops.lora_add_(y.clone(), x, A, B, scale, routing, kernel="fused"), want)
+                arms = {k: _graphed(lambda k=k: ops.lora_add_(y, x, A, B, scale, routing, kernel=k))
+                        for k in ("two_pass", "fused")}
+                times = {k: [] for k in arms}
+                for rep in range(rounds + 1):  # the first window warms up
+                    for k, replay in arms.items():
+                        t = _time(replay, iters) / GRAPH_CALLS
+                        if rep:
+                            times[k].append(t)
+                row.update({f"{pattern}_{k}_us": round(statistics.median(v), 2) for k, v in times.items()})
+                row[f"{pattern}_tiles"] = routing.n_tiles
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def graph_e2e_bench(name, batches, new_tokens, prompt_len, reps):
+    """``generate`` tokens/s with every sequence on its own adapter, graphed against eager (what a LoRA round
+    did before it had a graph), and against the graphed base (the LoRA model with no adapter named: the plain
+    graph). bf16 weights; each arm keeps its cache, so its graphs, from one repetition to the next."""
+    from ray_community_amd.models import PagedKVCache
+
+    rows = []
+    torch.manual_seed(0)
+    model = build_llama(name, device="cuda").eval()
+    model.enable_lora_(max_adapters=max(batches), max_rank=RANK)
+    distinct = [LoraAdapter.random(model.cfg, RANK, seed=i) for i in range(4)]
+    for i in range(max(batches)):
+        model.load_adapter(f"ad{i}", distinct[i % 4])
+    for B in batches:
+        g = torch.Generator().manual_seed(B)
+        prompts = torch.randint(0, model.cfg.vocab_size, (B, prompt_len), generator=g).tolist()
+        own = [f"ad{i}" for i in range(B)]
+        blocks = B * (-(-(prompt_len + new_tokens) // 16))
+        arms = {"graph_base": dict(graph_decode=True), "eager_lora": dict(adapters=own),
+                "graph_lora": dict(adapters=own, graph_decode=True)}
+        caches = {arm: PagedKVCache(model.cfg, blocks, 16, device="cuda", dtype=model.embed.weight.dtype) for arm in arms}
+        secs, toks = {arm: [] for arm in arms}, {}
+        for rep in range(reps + 2):  # two repetitions warm up: the eager step of a width, then its capture
+            for arm, kw in arms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                toks[arm] = model.generate(prompts, new_tokens, cache=caches[arm], **kw)
+                torch.cuda.synchronize()
+                if rep > 1:
+                    secs[arm].append(time.perf_counter() - t0)
+        assert toks["graph_lora"] == toks["eager_lora"]
+        med = {arm: statistics.median(v) for arm, v in secs.items()}
+        stats = next(iter(caches["graph_lora"]._decode_runners.values())).stats
+        rows.append(dict(model=name, batch=B, new_tokens=new_tokens, prompt_len=prompt_len,
+                         **{f"{arm}_tok_s": round(B * new_tokens / med[arm], 1) for arm in med},
+                         **{f"{arm}_min_max_s": [round(min(v), 4), round(max(v), 4)] for arm, v in secs.items()},
+                         lora_extra_us_per_step_graph=round((med["graph_lora"] - med["graph_base"]) / new_tokens * 1e6, 1),
+                         lora_extra_us_per_step_eager=round((med["eager_lora"] - med["graph_base"]) / new_tokens * 1e6, 1),
+                         graph_lora_stats=dict(stats), m_lora_fused=ops.M_LORA_FUSED))
+        print(json.dumps(rows[-1]), flush=True)
+    del model
+    torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=10)
@@ -147,7 +248,21 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=32)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--graph", action="store_true", help="the graph arm: fused against two-pass under a graph, "
+                    "and graphed LoRA generate against eager LoRA and the graphed base")
     args = ap.parse_args()
+    if args.graph:
+        result = {"device": torch.cuda.get_device_name(0), "rank": RANK, "m_lora_fused": ops.M_LORA_FUSED, "op": [],
+                  "generate": []}
+        if not args.no_op:
+            result["op"] = graph_op_bench("llama3-8b", args.rounds, args.iters)
+        if not args.no_e2e:
+            for name in args.models.split(","):
+                result["generate"] += graph_e2e_bench(name, (1, 32), args.new_tokens, args.prompt_len, args.reps)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(result, f, indent=1)
+        return
     floor_us = launch_floor(args.rounds, args.iters)
     result = {"device": torch.cuda.get_device_name(0), "rank": RANK, "launch_floor_us": round(floor_us, 2), "op": [],
               "generate": []}
